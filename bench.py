@@ -2,7 +2,12 @@
 """bench.py -- the north-star measurement (BASELINE.json): GStencil/s and achieved HBM GB/s
 vs the MI355X roofline on 3d7pt_star, fp32.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps of the headline kernel and prints one JSON line.  --full adds
+everything else this file measures or checks: the side kernels, the comparison of the timed launch with the gold kernel
+and the CPU oracle, the CPU baseline, and for N > 1 the N = 1 reference, the other exchange mode and the self-check.
+--dump-outputs DIR (N = 1) writes what the timed path left in A and B after its last step as DIR/<name>.npy.
 
 Workload (config.workload): C4 = 3d7pt_star 1024^3 fp32, `iterations 4` (the configuration
 the metric is quoted on; 8 GiB for the two buffers, fits one GPU).  One "step" = the
@@ -210,6 +215,36 @@ def slab_alone_options(workload, world, weak=False):
 
 MIN_WARM_S = 0.25     # untimed warm-up continues (beyond --warmup steps) until the GPU has been busy this long
 HBM_PEAK_GBS = 8000.0  # MI355X HBM3E peak (MI355X_MICROARCH.md: 8.0 TB/s spec)
+DUMP_MAX_BYTES = 64 << 20     # --dump-outputs: every file together
+DUMP_SAMPLE = 1 << 21         # ... elements per array when the whole arrays do not fit, at fixed positions drawn with DUMP_SEED
+DUMP_SEED = 20250101
+
+
+def dump_outputs(torch, out_dir, arrays):
+    """--dump-outputs: write {name: tensor} as out_dir/<name>.npy (float32 / float64).  Arrays that fit DUMP_MAX_BYTES together are
+    written whole, in their own shape; otherwise every array is written at the same fixed, seeded sample of flat positions (sorted,
+    without repeats), which go to out_dir/sample_flat_index.npy as float64 (exact below 2^53).  Returns what was written."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    ts = list(arrays.values())
+    for t in ts:
+        assert t.dtype in (torch.float32, torch.float64) and t.numel() == ts[0].numel(), (t.dtype, t.shape)
+    total = sum(t.numel() * t.element_size() for t in ts)
+    idx = None
+    if total > DUMP_MAX_BYTES:
+        n = min(DUMP_SAMPLE, DUMP_MAX_BYTES // (8 + sum(t.element_size() for t in ts)))
+        idx = np.unique(np.random.default_rng(DUMP_SEED).integers(0, ts[0].numel(), n, dtype=np.int64))
+        np.save(os.path.join(out_dir, "sample_flat_index.npy"), idx.astype(np.float64))
+        idx_dev = torch.from_numpy(idx).to(ts[0].device)
+    files = {}
+    for name, t in arrays.items():
+        host = (t.detach() if idx is None else t.detach().reshape(-1)[idx_dev]).cpu().numpy()
+        np.save(os.path.join(out_dir, name + ".npy"), host)
+        files[name + ".npy"] = list(host.shape)
+    if idx is not None:
+        files["sample_flat_index.npy"] = [int(idx.size)]
+    return {"dir": out_dir, "files": files, "sampled": idx is not None,
+            "sample_seed": DUMP_SEED if idx is not None else None}
 
 
 def kernels():
@@ -491,7 +526,7 @@ def parse_args(argv=None):
     ap.add_argument("--workload", default="c4", choices=sorted(WORKLOADS))
     ap.add_argument("--trial-steps", type=int, default=3, help="N > 1 with --exchange-every 0: steps of the run itself timed in each exchange mode before the timed loop (the faster mode is taken)")
     ap.add_argument("--kernel-args", default=None, help="override the generator options (space separated)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU leg (the oracle's baseline and its check of the timed launch)")
     ap.add_argument("--scaling", default="strong", choices=["strong", "weak"],
                     help="N > 1: strong = the workload's grid cut into N slabs (default, SURVEY 8e); weak = every rank holds a full-size slab (grid L*N planes)")
     ap.add_argument("--exchange-every", type=int, default=0, choices=[0, 1, 2],
@@ -503,12 +538,23 @@ def parse_args(argv=None):
     ap.add_argument("--placement", default="measured", choices=["measured", "kernel", "separate"],
                     help="N = 1: where the output array sits relative to the input array (launch time depends on (out - in) mod 64 MiB): measured on "
                          "this device before the timed region (default), the kernel's own recommendation, or two separate allocations")
-    ap.add_argument("--headline-only", action="store_true", help="skip the side measurements (profiling runs: one dr_ kernel in the trace)")
-    ap.add_argument("--no-verify", action="store_true", help="skip the post-loop comparison of the timed kernel with the gold kernel and the oracle")
+    ap.add_argument("--headline-only", action="store_true", help="with --full: skip the side measurements (a plain run has none)")
+    ap.add_argument("--no-verify", action="store_true", help="with --full: skip the post-loop comparison of the timed kernel with the gold kernel and the oracle")
     ap.add_argument("--n1-value", type=float, default=None, help="N > 1: the N = 1 value of the same workload; the line then carries value / (N * n1) as efficiency_vs_n1")
     ap.add_argument("--rank-timeout", type=float, default=900.0, help="N > 1 as a plain command: wall-clock limit for the rank processes this launcher starts (then terminate, kill, exit 124)")
     ap.add_argument("--prebuild-only", action="store_true", help="build (or find cached) every kernel the run needs for all --gpus ranks, then exit; no GPU is touched")
-    return ap.parse_args(argv)
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: the side kernels, the checks of the timed launch against the gold kernel and the CPU oracle, the CPU "
+                         "baseline; N > 1: the N = 1 reference, the exchange mode not chosen, the launch timeline and the self-check of the decomposed run")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="N = 1: after the timed steps, write what the timed path left in A (its result) and B after its last step as DIR/A.npy, "
+                         "DIR/B.npy (whole, or a fixed seeded sample with DIR/sample_flat_index.npy; 64 MiB at most)")
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and args.gpus > 1:
+        ap.error("--dump-outputs writes the single-GPU run's arrays (--gpus 1)")
+    return args
 
 
 def child_command(argv):
@@ -640,14 +686,15 @@ def main(argv=None):
     kern1 = kernf = kernw = kernp = None
     kernts = []
     kern3 = []
+    sides = args.full and not args.kernel_args and not args.headline_only      # the side measurements: --full only
     if pworld == 1:
         kern = drs.Kernel(opts + [w["stc"]])
-        if args.workload in STEP1 and not args.kernel_args and not args.headline_only:
+        if args.workload in STEP1 and sides:
             kern1 = drs.Kernel(STEP1[args.workload] + [w["stc"]])
             kernf = drs.Kernel(TEMPORAL2[args.workload] + [w["stc"]])
-        if args.workload in TEMPORALS and not args.kernel_args and not args.headline_only:
+        if args.workload in TEMPORALS and sides:
             kernts = [(st_, drs.Kernel(o_ + [w["stc"]]), o_) for st_, o_ in TEMPORALS[args.workload]]
-        if not args.kernel_args and not args.headline_only:
+        if sides:
             for o3 in FUSED3.get(args.workload, []):
                 try:
                     kern3.append((drs.Kernel(o3 + [w["stc"]]), o3))
@@ -666,7 +713,7 @@ def main(argv=None):
         sweep = HipSweep(w["stc"], opts, os.path.join(ROOT, "drstencil_amd", "_kcache"),
                          alone_opts=None if args.kernel_args else slab_alone_options(args.workload, pworld, args.scaling == "weak"))
         kern_n1 = None
-        if not args.kernel_args and args.scaling != "weak":
+        if args.full and not args.kernel_args and args.scaling != "weak":
             kern_n1 = drs.Kernel(TUNED[args.workload] + [w["stc"]])      # rank 0 measures the same box's single-GPU rate before the slab run
         if args.slab_runtime == "native" and args.scaling == "weak":
             raise SystemExit("bench.py: --slab-runtime native runs the spec's own grid (strong scaling)")
@@ -676,7 +723,7 @@ def main(argv=None):
                 if os.environ.get("DRS_EXP_SLAB") == "folded":        # timing experiment (multigpu.SlabRun.launch): boundary + interior as one view
                     sp_ = SlabPlan(L if w["ndim"] == 3 else M, H, pworld, r, ev)
                     sweep.kernel((sp_.bot[1] if sp_.bot else sp_.interior[1]) - (sp_.top[0] if sp_.top else sp_.interior[0]))
-            if not args.no_verify and not rehearse:       # the wider no-exchange slab of verify_slab_run
+            if args.full and not args.no_verify and not rehearse:       # the wider no-exchange slab of verify_slab_run
                 vlo, vhi = slab_verify_view(L if w["ndim"] == 3 else M, H, spec.launches, pworld, r)
                 sweep.kernel(vhi - vlo)
     if args.prebuild_only:
@@ -783,6 +830,8 @@ def main(argv=None):
             ev_ms += e0.elapsed_time(e1)
             done += min(chunk, args.steps - done)
         assert n == launches_per_step * args.steps
+        # what the timed path computed in its last step, before anything else runs on these arrays: the loop's result is in A
+        dumped = dump_outputs(torch, args.dump_outputs, {"A": A, "B": B}) if args.dump_outputs else None
         kinfo = kern.info
         kres = kern.resources
         parallelism = "1 GPU"
@@ -875,7 +924,7 @@ def main(argv=None):
                 fused3["verified_vs_gold_kernel_full_grid_bit_exact"] = bool(torch.equal(B, G3))
                 del G3
         verified, verification, host_slab, first_out = None, None, None, None
-        if not args.no_verify:
+        if args.full and not args.no_verify:
             g = torch.Generator(device=dev).manual_seed(1)
             A.copy_(torch.rand(shape, dtype=tdt, device=dev, generator=g))      # the input the timed loop started from
             verified, verification, host_slab, first_out = verify_timed_kernel(torch, kern, args.workload, A, B, kinfo.get("stages", 1) > 1)
@@ -965,6 +1014,7 @@ def main(argv=None):
             return el_, e0_.elapsed_time(e1_), n_
 
         run_alt = None
+        dumped = None
         if auto_every:
             # (1) the model: sweep / exchange / boundary times measured piecewise, MAX over ranks (multigpu.decide_exchange_every);
             # (2) the trial: the run itself in BOTH modes for a few steps between barriers -- first contact with a real link is not the
@@ -1013,7 +1063,7 @@ def main(argv=None):
         el, ev_ms = float(t[0]), float(t[1])
         # A/B in the same run: the mode that was NOT chosen, same protocol, same number of steps (side measurement: `value` is the chosen mode's)
         exchange_ab = None
-        if run_alt is not None:
+        if run_alt is not None and args.full:
             fill_finite(run_alt, 101 + prank)
             for _ in range(2):
                 run_alt.run()
@@ -1024,7 +1074,7 @@ def main(argv=None):
             exchange_ab = {"every_%d_ms_per_step" % run.plan.every: el * 1e3 / args.steps, "every_%d_ms_per_step" % run_alt.plan.every: float(ta[0]) * 1e3 / args.steps,
                            "value_is": "every_%d" % run.plan.every, "steps_each": args.steps}
         # what one exchanging launch is made of, per rank (collective: the exchanges pair up), and who the ranks are
-        tl = run.timeline(4) if hasattr(run, "timeline") else None
+        tl = run.timeline(4) if args.full and hasattr(run, "timeline") else None
         try:
             rccl = ".".join(str(x) for x in torch.cuda.nccl.version()) if backend == "nccl" else backend
         except Exception as e:
@@ -1042,7 +1092,7 @@ def main(argv=None):
         step1 = fused2 = window2 = fused3 = prev_headline = None
         temporals = {}
         verified, verification, host_slab, first_out = None, None, None, None     # the slab kernels' parity is tests/test_gpu_parity.py::test_c4_slab_views_at_full_size
-        if not args.no_verify and not rehearse:      # (a rehearsal's self-neighbour exchange is not the physical one)
+        if args.full and not args.no_verify and not rehearse:      # (a rehearsal's self-neighbour exchange is not the physical one)
             verified, verification = verify_slab_run(torch, dist, run, sweep, (L, M, N) if w["ndim"] == 3 else (M, N), H, launches_per_step, iters, prank, pworld, dev, tdt,
                                                      workload=None if args.kernel_args else args.workload, step=step)
 
@@ -1077,7 +1127,10 @@ def main(argv=None):
                          "algorithmic_bytes_per_launch": alg_bytes, "avg_launch_ms": avg_launch_s * 1e3},
             "verification": verification,
             "device": device_info(torch, dev),
+            "full": args.full,
         }
+        if dumped is not None:
+            out["outputs_dumped"] = dumped
         if pworld == 1:
             out["config"]["placement"] = placement
             out["config"]["finite_data"] = {"overflow_horizon_time_steps": finite_steps, "time_steps_per_step": launches_per_step * step, "steps_per_chunk": chunk,
@@ -1111,7 +1164,7 @@ def main(argv=None):
         sides_ = [v_ for v_ in (step1, fused2, window2, prev_headline, fused3) + tuple(temporals.values()) if v_ and "verified_vs_gold_kernel_full_grid" in v_]
         if sides_:
             out["side_kernels_verified"] = all(v_["verified_vs_gold_kernel_full_grid"]["ok"] for v_ in sides_)
-        if not args.no_cpu_baseline and pworld == 1:
+        if args.full and not args.no_cpu_baseline and pworld == 1:
             sys.path.insert(0, ROOT)
             out["cpu_baseline"], oracle_check = cpu_baseline(args.workload, step, host_slab=host_slab, gpu_first_launch=first_out, temporal=kinfo.get("stages", 1) > 1)
             if oracle_check is not None:       # the CPU leg is also the checker of what was timed

@@ -188,13 +188,15 @@ def _run_gpus_host():
 
 def _run_bench_rehearsal():
     """bench.py's N > 1 branch as a child process (rank 1 of 4 on this one GPU, self-neighbour exchange through a real RCCL
-    process group), before this process touches HIP: the test reads what arrived on its stdout."""
+    process group), before this process touches HIP: the test reads what arrived on its stdout.  These runs check what only
+    `bench.py --full` does (the N = 1 reference, the self-checks); the last one is a plain run with --dump-outputs."""
+    import shutil
     import subprocess
     out = os.path.join(ROOT, "drstencil_amd", "_kcache", "bench_rehearsal")
     os.makedirs(out, exist_ok=True)
     env = dict(os.environ, DRS_REHEARSE="1/4", MASTER_ADDR="127.0.0.1")
     try:
-        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "4", "--steps", "2", "--warmup", "1", "--no-cpu-baseline"],
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "4", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--full"],
                            env=env, capture_output=True, text=True, timeout=300)
         stdout, text = r.stdout, "[rc=%d]\n%s" % (r.returncode, r.stderr[-1500:])
     except Exception as e:
@@ -210,7 +212,7 @@ def _run_bench_rehearsal():
     env2 = dict(os.environ, DRS_BENCH_BACKEND="gloo", DRS_BENCH_ONE_GPU="1")
     try:
         r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port", "29631",
-                            os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--no-cpu-baseline"],
+                            os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--full"],
                            env=env2, capture_output=True, text=True, timeout=420, cwd=ROOT)
         stdout, text = r.stdout, "[rc=%d]\n%s" % (r.returncode, r.stderr[-1500:])
     except Exception as e:
@@ -218,7 +220,7 @@ def _run_bench_rehearsal():
     # ... and the single-GPU line with a step count beyond the overflow horizon of the data (coefficients sum to 1.5: all inf after ~218 time
     # steps): the timed loop must run in chunks, each from the restored pristine input
     try:
-        r1 = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "60", "--warmup", "1", "--no-cpu-baseline", "--headline-only"],
+        r1 = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "60", "--warmup", "1", "--no-cpu-baseline", "--headline-only", "--full"],
                             capture_output=True, text=True, timeout=300, cwd=ROOT)
         with open(os.path.join(out, "n1_steps60_stdout.txt"), "w") as f:
             f.write(r1.stdout)
@@ -230,6 +232,19 @@ def _run_bench_rehearsal():
     with open(os.path.join(out, "two_ranks_stdout.txt"), "w") as f:
         f.write(stdout)
     with open(os.path.join(out, "two_ranks_stderr.txt"), "w") as f:
+        f.write(text)
+    # ... and a plain single-GPU run (the headline only) that writes what its timed path computed
+    dump = os.path.join(out, "plain_dump")
+    shutil.rmtree(dump, ignore_errors=True)
+    try:
+        r2 = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--dump-outputs", dump],
+                            capture_output=True, text=True, timeout=300, cwd=ROOT)
+        stdout, text = r2.stdout, "[rc=%d]\n%s" % (r2.returncode, r2.stderr[-1500:])
+    except Exception as e:
+        stdout, text = "", "[exception] %r" % (e,)
+    with open(os.path.join(out, "plain_stdout.txt"), "w") as f:
+        f.write(stdout)
+    with open(os.path.join(out, "plain_stderr.txt"), "w") as f:
         f.write(text)
 
 

@@ -127,3 +127,41 @@ def test_oracle_slab_checker_compares_in_chunks():
         assert bench.oracle_check_slabs("_chunk_test", 1, [{"label": "whole_grid", "z0": 0, "input": src, "output": bad_out}], True)["ok"]
     finally:
         del bench.WORKLOADS["_chunk_test"]
+
+
+def test_dump_outputs_writes_whole_arrays_or_one_fixed_sample(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: arrays that fit DUMP_MAX_BYTES together are written whole, in their shape; larger ones at the same fixed,
+    seeded sample of flat positions in every file and every run (the positions beside them), never more than DUMP_MAX_BYTES in all."""
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    a, b = torch.rand((3, 5, 7), dtype=torch.float64), torch.rand((3, 5, 7), dtype=torch.float64)
+    info = bench.dump_outputs(torch, str(tmp_path / "small"), {"A": a, "B": b})
+    assert info["sampled"] is False and sorted(os.listdir(tmp_path / "small")) == ["A.npy", "B.npy"]
+    assert np.array_equal(np.load(tmp_path / "small" / "A.npy"), a.numpy()) and np.array_equal(np.load(tmp_path / "small" / "B.npy"), b.numpy())
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 4096)
+    monkeypatch.setattr(bench, "DUMP_SAMPLE", 100)
+    big = torch.arange(10000, dtype=torch.float32).reshape(100, 100)
+    for run in ("one", "two"):
+        info = bench.dump_outputs(torch, str(tmp_path / run), {"A": big, "B": 2 * big})
+        assert info["sampled"] is True and info["sample_seed"] == bench.DUMP_SEED
+        assert sum(os.path.getsize(tmp_path / run / f) for f in os.listdir(tmp_path / run)) <= 4096
+    idx = np.load(tmp_path / "one" / "sample_flat_index.npy")
+    assert idx.dtype == np.float64 and 90 <= idx.size <= 100 and np.all(np.diff(idx) > 0)
+    for f in ("sample_flat_index.npy", "A.npy", "B.npy"):
+        assert np.array_equal(np.load(tmp_path / "one" / f), np.load(tmp_path / "two" / f))
+    A, B = np.load(tmp_path / "one" / "A.npy"), np.load(tmp_path / "one" / "B.npy")
+    assert A.dtype == np.float32 and np.array_equal(A, idx.astype(np.float32)) and np.array_equal(B, 2 * A)
+
+
+def test_plain_run_is_the_default_and_full_is_an_option():
+    sys.path.insert(0, ROOT)
+    import bench
+    a = bench.parse_args(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert a.full is False and a.dump_outputs is None and a.steps == 7 and a.warmup == 2
+    a = bench.parse_args(["--steps", "7", "--full", "--dump-outputs", "out"])
+    assert a.full is True and a.dump_outputs == "out"
+    for bad in (["--steps", "0"], ["--gpus", "2", "--dump-outputs", "out"]):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + bad, capture_output=True, text=True, timeout=60)
+        assert r.returncode == 2 and "error" in r.stderr

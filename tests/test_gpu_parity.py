@@ -557,6 +557,42 @@ def test_two_rank_processes_under_the_launcher_verify_themselves():
     assert "REHEARSAL: 2 rank processes on ONE GPU" in rec["config"]["parallelism"] and rec["efficiency_vs_n1"] > 0
 
 
+def test_plain_bench_run_is_lean_and_dumps_what_its_timed_path_computed(torch_cuda):
+    """`bench.py --steps 3 --warmup 1 --dump-outputs DIR` at session start (conftest._run_bench_rehearsal): a plain run times the headline
+    only -- no side kernels, checks or CPU baseline in its line -- and DIR holds A and B after its last timed step at a fixed, seeded sample
+    of positions (two 1024^3 arrays do not fit 64 MiB).  Recomputed here with the gold kernel from the same seeded input (the timed loop
+    starts from it; three runs of the reference's loop): bit for bit."""
+    import bench
+    import drstencil_amd as drs
+    torch = torch_cuda
+    d = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "drstencil_amd", "_kcache", "bench_rehearsal")
+    err = open(os.path.join(d, "plain_stderr.txt")).read()
+    assert err.startswith("[rc=0]"), err[-1500:]
+    lines = open(os.path.join(d, "plain_stdout.txt")).read().splitlines()
+    assert len(lines) == 1
+    rec = json.loads(lines[0])
+    assert rec["steps"] == 3 and rec["full"] is False and rec["unit"] == "GStencil/s" and rec["dtype"] == "f32" and rec["value"] > 0
+    assert abs(rec["ms_per_step"] / (2 * rec["roofline"]["avg_launch_ms"]) - 1.0) < 0.05
+    assert rec["verified"] is None and rec["cpu_baseline"] is None and rec["step1_kernel"] is None and rec["fused_multistep_kernel"] is None
+    dump = os.path.join(d, "plain_dump")
+    assert rec["outputs_dumped"]["sampled"] is True and sorted(os.listdir(dump)) == ["A.npy", "B.npy", "sample_flat_index.npy"]
+    assert sum(os.path.getsize(os.path.join(dump, f)) for f in os.listdir(dump)) <= bench.DUMP_MAX_BYTES
+    idx = np.load(os.path.join(dump, "sample_flat_index.npy"))
+    a, b = np.load(os.path.join(dump, "A.npy")), np.load(os.path.join(dump, "B.npy"))
+    assert idx.dtype == np.float64 and a.dtype == b.dtype == np.float32 and a.shape == b.shape == idx.shape and idx.size > 2_000_000
+    w = bench.WORKLOADS["c4"]
+    kern = drs.Kernel(bench.TUNED["c4"] + [w["stc"]])
+    shape = (kern.info["L"], kern.info["M"], kern.info["N"])
+    A = torch.rand(shape, dtype=torch.float32, device="cuda:0", generator=torch.Generator(device="cuda:0").manual_seed(1))
+    B = torch.zeros_like(A)
+    for _ in range(3):
+        kern.run(A.data_ptr(), B.data_ptr(), gold=True)
+    torch.cuda.synchronize()
+    it = torch.from_numpy(idx.astype(np.int64)).to("cuda:0")
+    assert np.array_equal(A.reshape(-1)[it].cpu().numpy(), a) and np.array_equal(B.reshape(-1)[it].cpu().numpy(), b)
+    assert np.isfinite(a).all() and np.count_nonzero(a) > 0.9 * a.size
+
+
 def test_emitted_n_gpu_host():
     """`drstencil --gpus N` (round 3): the emitted program whose main() is launcher and ranks in one, on the C ABI's drs_slab_* entry
     points -- run at session start by scripts/try_gpus_host.sh on this one GPU."""
