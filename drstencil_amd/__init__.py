@@ -61,6 +61,7 @@ def lib():
     L.drs_kernel_launch.argtypes = [vp, vp, vp, vp]
     L.drs_kernel_launch_gold.argtypes = [vp, vp, vp, vp]
     L.drs_kernel_launch_pair.argtypes = [vp, vp, vp, vp, vp, vp]
+    L.drs_kernel_wrap.argtypes = [vp, vp, vp]
     L.drs_kernel_run.argtypes = [vp, vp, vp, ci, ci, vp]
     L.drs_kernel_run_timed.argtypes = [vp, vp, vp, ci, ci, vp, ctypes.POINTER(ctypes.c_float)]
     L.drs_slab_unique_id.argtypes = [vp]
@@ -92,7 +93,7 @@ EXPORTS = [
     "drs_spec_open", "drs_spec_close", "drs_spec_halo", "drs_spec_dist", "drs_spec_range", "drs_spec_npoints",
     "drs_spec_iterations", "drs_spec_launches", "drs_spec_dims", "drs_spec_point", "drs_spec_partition",
     "drs_kernel_build", "drs_kernel_close", "drs_kernel_unload", "drs_kernel_info", "drs_kernel_path", "drs_kernel_resources", "drs_kernel_pair_layout", "drs_kernel_launch", "drs_kernel_launch_pair",
-    "drs_kernel_launch_gold", "drs_kernel_run", "drs_kernel_run_timed",
+    "drs_kernel_wrap", "drs_kernel_launch_gold", "drs_kernel_run", "drs_kernel_run_timed",
     "drs_fill_random_f64", "drs_fill_random_f32", "drs_check_error_f64", "drs_check_error_f32",
     "drs_slab_unique_id", "drs_slab_open", "drs_slab_plan", "drs_slab_connect", "drs_slab_run", "drs_slab_sync", "drs_slab_stream", "drs_slab_info",
     "drs_slab_error", "drs_slab_close",
@@ -218,6 +219,20 @@ class Kernel:
         rc = lib().drs_kernel_launch_pair(self.h, d_in0, d_out0, d_in1, d_out1, stream)
         if rc != 0:
             raise RuntimeError("pair launch error %d (-2: kernel built without --pair-launch 1)" % rc)
+
+    @property
+    def periodic(self):
+        """True for kernels generated with --boundary periodic: every launch first fills the input's ring from its interior (wrap())."""
+        return self.info.get("boundary") == "periodic"
+
+    def wrap(self, d, stream=0):
+        """--boundary periodic: fill the ring of width Halo of the device array `d` with the periodic images of its interior (period
+        dim - 2 Halo per dimension), asynchronously on `stream`.  Every launch does this to its input first."""
+        rc = lib().drs_kernel_wrap(self.h, d, stream)
+        if rc == -2:
+            raise RuntimeError("wrap(): the kernel was not generated with --boundary periodic")
+        if rc != 0:
+            raise RuntimeError("HIP launch error %d" % rc)
 
     def launch_gold(self, d_in, d_out, stream=0):
         rc = lib().drs_kernel_launch_gold(self.h, d_in, d_out, stream)

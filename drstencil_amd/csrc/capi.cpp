@@ -34,6 +34,7 @@ struct drs_kernel {
     int (*launch)(const void *, void *, hipStream_t) = nullptr;
     int (*launch_gold)(const void *, void *, hipStream_t) = nullptr;
     int (*launch_pair)(const void *, void *, const void *, void *, hipStream_t) = nullptr;   // only with --pair-launch 1
+    int (*wrap)(void *, hipStream_t) = nullptr;              // only with --boundary periodic
     const char *(*info)(void) = nullptr;
     std::string path;
     std::string resources;   // JSON: register / scratch / LDS use of dr_<name> as reported by the compiler
@@ -338,6 +339,7 @@ drs_kernel *drs_kernel_build(int argc, const char *const *argv, const char *cach
     k->launch = (int (*)(const void *, void *, hipStream_t))dlsym(dl, "drs_plugin_launch");
     k->launch_gold = (int (*)(const void *, void *, hipStream_t))dlsym(dl, "drs_plugin_launch_gold");
     k->launch_pair = (int (*)(const void *, void *, const void *, void *, hipStream_t))dlsym(dl, "drs_plugin_launch_pair");
+    k->wrap = (int (*)(void *, hipStream_t))dlsym(dl, "drs_plugin_wrap");
     k->info = (const char *(*)(void))dlsym(dl, "drs_plugin_info");
     k->path = so;
     k->resources = resources;
@@ -394,6 +396,11 @@ int drs_kernel_launch_pair(drs_kernel *k, const void *d_in0, void *d_out0, const
     if (!k->launch_pair) return -2;      // the kernel was not generated with --pair-launch 1
     g_launched = true;
     return k->launch_pair(d_in0, d_out0, d_in1, d_out1, (hipStream_t)stream);
+}
+int drs_kernel_wrap(drs_kernel *k, void *d, void *stream) {
+    if (!k->wrap) return -2;             // the kernel was not generated with --boundary periodic
+    g_launched = true;
+    return k->wrap(d, (hipStream_t)stream);
 }
 int drs_kernel_launch_gold(drs_kernel *k, const void *d_in, void *d_out, void *stream) {
     g_launched = true;

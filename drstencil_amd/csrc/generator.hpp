@@ -102,6 +102,13 @@ Options:
 MI355X options:
 
 --dtype <fp32|fp64>     Element type (fp64 by default, as the reference).
+--boundary <fixed|periodic>  fixed (default): the ring of width Halo (= step * order) around the interior is input that no launch
+                        writes (the reference's semantics).  periodic: the interior is a periodic domain of period dim - 2 * Halo
+                        in every dimension (so the period depends on --step) and the ring holds its ghost copies: the ghost at x
+                        takes the value at x + P (x < Halo) or x - P (x >= dim - Halo), each coordinate wrapped on its own.  Every
+                        launch (in -> out) first refills in's ring from in's interior -- it OVERWRITES the input array's ring --
+                        then sweeps as with fixed; out's ring is not touched.  Needs every dimension >= 3 * Halo; not with
+                        --gpus N > 1 or --pair-launch 1.
 --xrim <lds|dpp>        x halo inside a wavefront by DPP wave shifts (default) or through LDS.
 --schedule <scatter|reuse|window>  How reuse along the streamed dimension is split between source planes kept on chip and
                         partial sums carried in VGPRs (results never depend on it):
@@ -212,7 +219,7 @@ inline GenResult generate(const std::vector<std::string> &args /* argv[1..] */) 
         };
         // options that NAME the problem or the artefact; every other option is a tuning choice and switches the tuned-defaults table off
         if (!(a == "-o" || a == "--3d" || a == "--step" || a == "--streaming" || a == "--check" || a == "--gold" || a == "--dtype" || a == "--gpus" ||
-              a == "--pair-launch" || a == "--temporal" || a == "--dist" || a == "--tuned-defaults" || a == "--out-skew")) o.tuning_given = true;
+              a == "--pair-launch" || a == "--temporal" || a == "--dist" || a == "--tuned-defaults" || a == "--out-skew" || a == "--boundary")) o.tuning_given = true;
         if (a == "-o") { if (i != argc - 2) { o.out_name = arg(++i); o.out_set = true; } }
         else if (a == "--3d") o.is3d = true;
         else if (a == "--step") { if (!int_opt(o.step, nullptr)) break; }
@@ -232,6 +239,7 @@ inline GenResult generate(const std::vector<std::string> &args /* argv[1..] */) 
         else if (a == "--gold") o.gold = true;
         // ---- additive options
         else if (a == "--dtype") { if (!str_opt(o.dtype)) break; }
+        else if (a == "--boundary") { if (!str_opt(o.boundary)) break; }
         else if (a == "--xrim") { if (!str_opt(o.xrim)) break; }
         else if (a == "--schedule") { if (!str_opt(o.schedule)) break; o.schedule_set = true; }
         else if (a == "--order") { if (!str_opt(o.order)) break; o.order_set = true; }
@@ -289,6 +297,7 @@ inline GenResult generate(const std::vector<std::string> &args /* argv[1..] */) 
     }
     if (illegal_exit) return res;
     if (o.dtype != "fp32" && o.dtype != "fp64") { res.messages += "Illegal input.\n"; res.exit_code = 255; return res; }
+    if (o.boundary != "fixed" && o.boundary != "periodic") { res.messages += "Illegal input.\n"; res.exit_code = 255; return res; }
     // an explicit --dist selects the reference's kind of reuse: `Range` source planes resident, the rest carried as partial sums
     if (!o.schedule_set && o.dist != 0) o.schedule = "reuse";
     if (o.schedule != "scatter" && o.schedule != "window" && o.schedule != "reuse") { res.messages += "Illegal input.\n"; res.exit_code = 255; return res; }
@@ -339,20 +348,38 @@ inline GenResult generate(const std::vector<std::string> &args /* argv[1..] */) 
     res.plan = make_plan(st, o, kernel_base_name(stcfile));
     if (!res.plan.error.empty()) { res.messages += "Invalid configuration!\n"; res.exit_code = 255; return res; }
     if (!res.plan.note.empty()) res.messages += "drstencil: note: " + res.plan.note + "\n";
+    // `--boundary fixed` is the default spelled out: it leaves no trace in the emitted source (banner and slab host alike)
+    auto fixed_boundary = [&](size_t i) { return args[i] == "--boundary" && i + 2 < args.size() && args[i + 1] == "fixed"; };
     std::string cmdline;
-    for (size_t i = 0; i + 1 < args.size(); i++) cmdline += (i ? " " : "") + args[i];
+    for (size_t i = 0, n = 0; i + 1 < args.size(); i++) {
+        if (fixed_boundary(i)) { i++; continue; }
+        cmdline += (n++ ? " " : "") + args[i];
+    }
     for (size_t i = 0; i + 1 < args.size(); i++) {
-        if (args[i] == "-o" || args[i] == "--gpus") { i++; continue; }
+        if (args[i] == "-o" || args[i] == "--gpus" || fixed_boundary(i)) { i++; continue; }
         if (args[i] == "--check" || args[i] == "--gold") continue;
         o.slab_args.push_back(args[i]);
     }
     if (o.gpus < 1 || o.gpus > 64) { res.messages += "Illegal input.\n"; res.exit_code = 255; return res; }
+    if (res.plan.periodic && (o.gpus > 1 || o.pair_launch)) {
+        // periodic z (y in 2D) across ranks would need a rank 0 <-> rank N-1 exchange; the pair kernel exists only for slab views
+        res.messages += "Invalid configuration!\n"; res.exit_code = 255;
+        res.plan.error = o.gpus > 1 ? "--boundary periodic cannot be combined with --gpus N > 1 (the slab runtime has no periodic exchange)"
+                                    : "--boundary periodic cannot be combined with --pair-launch 1 (the pair kernel serves the slab runtime, which has no periodic exchange)";
+        return res;
+    }
     HipEmitter em(res.plan, o);
     if (!em.config_error().empty()) { res.messages += "Invalid configuration!\n"; res.exit_code = 255; res.plan.error = em.config_error(); return res; }
     if (em.lds_bytes() > 160 * 1024) {   // gfx950: 160 KiB of LDS per workgroup
         res.messages += "Invalid configuration!\n"; res.exit_code = 255; res.plan.error = "tile needs more than 160 KiB of LDS"; return res;
     }
     res.source = em.source(stcfile, cmdline);
+    if (res.plan.periodic) {
+        const int H = st.halo;
+        std::string per = st.ndim == 3 ? std::to_string(st.L - 2 * H) + " x " : "";
+        per += std::to_string(st.M - 2 * H) + " x " + std::to_string(st.N - 2 * H);
+        res.notes += "drstencil: note: periodic boundaries: period " + per + ", ring of width " + std::to_string(H) + " holds ghost copies\n";
+    }
     res.out_name = o.out_name;
     res.emitted = true;
     return res;

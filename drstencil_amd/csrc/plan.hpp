@@ -166,6 +166,9 @@ struct GenOptions {
                                  // instead of write / barrier / read once per stage; costs stages - 1 more prologue iterations per stream block
     int coef_sgpr = 0;           // --coef sgpr: fp32 coefficient values in scalar registers instead of 32-bit literals (4-byte instead of 8-byte FMAs)
     int row_fence = 0;           // mask of __builtin_amdgcn_sched_barrier between row groups (0: nothing crosses; -1: no fence)
+    std::string boundary = "fixed";   // --boundary fixed: the ring of width Halo is frozen input (the reference's Dirichlet boundary);
+                                 // periodic: the ring holds ghost copies of the interior, refilled from the input's interior by wrap_<name> at the
+                                 // start of every launch (period dim - 2 Halo per dimension).  It names the problem, not a tuning choice
 };
 
 struct Tap {
@@ -215,6 +218,7 @@ struct KernelPlan {
     double drift_estimate = 0.0;     // predicted max relative distance from the fused arithmetic after the spec's iterations (0: gold order)
     double drift_per_launch = 0.0;   // the same after one launch (grows ~ launches^0.62)
     int horizon_iterations = -1;     // largest `iterations` for which the estimate stays within the bar (-1: unlimited, gold order)
+    bool periodic = false;   // --boundary periodic: every launch first fills the input's ring from its interior (wrap_<name>)
     std::string error;       // non-empty: invalid configuration
     std::string note;        // non-empty: something the user asked for was not done (printed by the generator, kept in the banner)
 };

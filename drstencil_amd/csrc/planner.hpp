@@ -266,6 +266,9 @@ inline KernelPlan make_plan(const Stencil &st, const GenOptions &o_in, const std
     p.NBY = p.has_y ? std::max(1, ceil_div(p.DY - H, p.OY)) : 1;
     p.NBS = p.has_s ? std::max(1, ceil_div(p.DS - 2 * H, p.SN)) : 1;
     if (p.DX - 2 * H < 1 || (p.has_y && p.DY - 2 * H < 1) || (p.has_s && p.DS - 2 * H < 1)) { p.error = "grid has no interior"; return p; }
+    // periodic: the period P = dim - 2 Halo must hold a ghost ring's worth of interior (P >= Halo), so that every ghost's source is interior
+    p.periodic = (o.boundary == "periodic");
+    if (p.periodic && (st.N < 3 * H || st.M < 3 * H || (st.ndim == 3 && st.L < 3 * H))) { p.error = "--boundary periodic needs every dimension >= 3 * Halo (period >= Halo)"; return p; }
 
     if (o.loader_waves > 0 && o.stage != "dma") { p.error = "--loader-waves goes with --stage dma"; return p; }
     if (o.stage == "dma") {

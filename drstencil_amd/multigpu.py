@@ -36,6 +36,14 @@ import os
 import drstencil_amd as drs
 
 
+def refuse_periodic(opts, who):
+    """--boundary periodic has no slab form: the periodic outer faces would need a rank 0 <-> rank R-1 exchange."""
+    opts = list(opts or ())
+    if any(a == "--boundary" and i + 1 < len(opts) and opts[i + 1] == "periodic" for i, a in enumerate(opts)):
+        raise ValueError("%s: --boundary periodic is not supported by the slab decomposition (periodic z / y across ranks needs a "
+                         "rank 0 <-> rank R-1 exchange); run it on one GPU" % who)
+
+
 def slab_bounds(L, world, rank):
     """Planes [z0, z1) owned by `rank` (balanced split of the outermost dim)."""
     return (rank * L) // world, ((rank + 1) * L) // world
@@ -277,6 +285,8 @@ class HipSweep:
         """alone_opts: generator options for launches that run with NO exchange beside them (the whole-slab launch of an
         every = 2 pair): e.g. one stream block per tile, which sweeps a slab 7 % faster but whose long-lived workgroups would
         keep the RCCL send/recv kernel off the CUs."""
+        refuse_periodic(opts, "HipSweep")
+        refuse_periodic(alone_opts, "HipSweep")
         self.base_stc, self.opts, self.cache_dir = base_stc, list(opts), cache_dir
         self.alone_opts = list(alone_opts) if alone_opts else None
         self.ndim = 3 if "--3d" in self.opts else 2
@@ -389,6 +399,7 @@ class SlabRun:
     def __init__(self, torch, dist, dims, H, step, iterations, rank, world, sweep, device, dtype, every=1):
         """dims = (L, M, N) for a 3D run cut along z, or (M, N) for a 2D run cut along y; every = launches per
         exchange (1 or 2, see SlabPlan)."""
+        refuse_periodic(getattr(sweep, "opts", None), "SlabRun")
         self.torch, self.dist = torch, dist
         dims = tuple(dims)
         self.plan = SlabPlan(dims[0], H, world, rank, every if world > 1 else 1)
@@ -577,6 +588,8 @@ class NativeSlabRun:
 
     def __init__(self, torch, dist, base_stc, opts, dims, H, step, iterations, rank, world, device, dtype, every=1, alone_opts=None,
                  rehearse_world=0, cache_dir=None):
+        refuse_periodic(opts, "NativeSlabRun")
+        refuse_periodic(alone_opts, "NativeSlabRun")
         self.torch, self.dist = torch, dist
         dims = tuple(dims)
         pworld = rehearse_world or world

@@ -63,7 +63,8 @@ int drs_kernel_unload(drs_kernel *k);
  *                                  iterations) stays within 1e-6 (fp32) / 1e-12 (fp64), "tolerance_horizon_iterations" is the
  *                                  largest iteration count for which it does, and "temporal_forced": 1 marks --temporal force.
  *   "out_skew_bytes", "placement_period_bytes": where the output array should sit relative to the input array, modulo the period
- *                                  (64 MiB): see drs_kernel_pair_layout below. */
+ *                                  (64 MiB): see drs_kernel_pair_layout below.
+ *   "boundary": "periodic", "period": [P...]   only for kernels generated with --boundary periodic (see drs_kernel_wrap). */
 const char *drs_kernel_info(const drs_kernel *k);
 const char *drs_kernel_path(const drs_kernel *k);   /* the loaded shared object */
 /* JSON: vgprs, agprs, sgprs, scratch_bytes_per_lane, sgpr_spill, vgpr_spill, occupancy_waves_per_simd, lds_bytes of
@@ -81,13 +82,24 @@ const char *drs_kernel_resources(const drs_kernel *k);
  * in = arena, out = arena + *out_offset (a multiple of the 64 MiB period that clears the array + the kernel's "out_skew_bytes"),
  * arena of *arena_bytes.  Advice only: every entry point accepts any two device pointers, results never depend on them. */
 int drs_kernel_pair_layout(const drs_kernel *k, size_t *arena_bytes, size_t *out_offset);
-/* one launch of dr_<name><<<grid, block, 0, stream>>>(in, out): codegen.hpp:577,582-583 */
+/* one launch of dr_<name><<<grid, block, 0, stream>>>(in, out): codegen.hpp:577,582-583.
+ * --boundary periodic kernels first run wrap_<name> on d_in (drs_kernel_wrap), so d_in's RING IS OVERWRITTEN although the
+ * parameter is const; the result depends only on d_in's interior, and d_out's ring is not touched.  The same holds for
+ * drs_kernel_launch_gold, drs_kernel_run and drs_kernel_run_timed, whose launches go through the same entry points. */
 int drs_kernel_launch(drs_kernel *k, const void *d_in, void *d_out, void *stream);
 /* one launch of dr2_<name>: the same sweep over TWO (in, out) pairs (kernels generated with --pair-launch 1; -2 otherwise).
  * No reference counterpart: the two boundary views of a slab-decomposed run (drstencil_amd/multigpu.py) in one launch. */
 int drs_kernel_launch_pair(drs_kernel *k, const void *d_in0, void *d_out0, const void *d_in1, void *d_out1, void *stream);
 /* one launch of gold_<name> (the reference's verification kernel, codegen.hpp:611-612) */
 int drs_kernel_launch_gold(drs_kernel *k, const void *d_in, void *d_out, void *stream);
+/* --boundary periodic (no reference counterpart: the reference's ring is a fixed Dirichlet boundary).  The grid's interior is a
+ * periodic domain of period P_d = dim_d - 2 * Halo in every dimension (Halo = step * order, so P depends on --step), and its ring
+ * of width Halo holds ghost copies: the ghost at coordinate x takes the value at w(x) = x + P (x < Halo), x - P (x >= dim - Halo),
+ * x otherwise, each coordinate wrapped on its own (edges and corners included).  One launch of wrap_<name> on d, asynchronous on
+ * `stream`: fills d's ring from d's interior (the interior is not written).  -2 when the kernel was not generated with
+ * --boundary periodic.  Such kernels need every dimension >= 3 * Halo; --gpus N > 1, --pair-launch 1 and the drs_slab_* runtime
+ * refuse them. */
+int drs_kernel_wrap(drs_kernel *k, void *d, void *stream);
 /* the timed ping-pong loop: for (t = 0; t < iterations; t += 2*step) { k(A,B); k(B,A); }
  * (codegen.hpp:581-584).  gold != 0 runs gold_<name> instead.  Returns the number of
  * launches, -1 on a HIP error, or -3 when `iterations` exceeds the tolerance horizon of a reassociated (temporal) kernel
