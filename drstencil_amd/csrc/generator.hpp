@@ -5,6 +5,7 @@
 // unknown flag is "Illegal input." exit 0; `-o` without a value is ignored), plus
 // additive MI355X options that the reference does not have.
 #pragma once
+#include <algorithm>
 #include <cmath>
 #include <fstream>
 #include <sstream>
@@ -198,136 +199,140 @@ MI355X options:
         )";
 }
 
-inline GenResult generate(const std::vector<std::string> &args /* argv[1..] */) {
-    GenResult res;
-    GenOptions &o = res.opt;
-    const int argc = (int)args.size() + 1;
-    auto arg = [&](int i) -> const std::string & { return args[i - 1]; };
-    if (argc < 2) { res.messages = "Please specify the .stc file.\n"; return res; }
-    if (arg(1) == "--help" || arg(1) == "-h") { res.messages = std::string(help_text()) + "\n"; return res; }
+// ---- the command's options, one row each: the spelling, where the value goes in GenOptions and the `*_set` marker it raises.  The
+// target's type is the kind: a bool is a flag (SET1: a flag that sets an int to 1); an int takes atoi of the next word; a string takes
+// the next word, from `pick` if given (checked after the scan); a setter takes it at once and rejects a bad value where the scan meets
+// it.  NAMES: the option names the problem or the artefact; every other option is a tuning choice and switches the tuned-defaults
+// table off.  LOCAL: kept out of the slab host's options (GenOptions::slab_args).  HIDDEN: not in help_text(), which is written by hand
+// (tests/test_cli_and_ir.py holds the two together).
+enum : unsigned { NAMES = 1, LOCAL = 2, HIDDEN = 4, SET1 = 8 };
+using Setter = bool (*)(GenOptions &, const std::string &);
+struct Opt {
+    const char *name;
+    unsigned attr = 0;
+    bool GenOptions::*b = nullptr;
+    int GenOptions::*i = nullptr;
+    std::string GenOptions::*s = nullptr;
+    const char *pick = nullptr;   // the values a string accepts, space-separated
+    Setter put = nullptr;
+    bool GenOptions::*mark = nullptr;
+    constexpr Opt(const char *n, bool GenOptions::*t, unsigned a = 0) : name(n), attr(a), b(t) {}
+    constexpr Opt(const char *n, int GenOptions::*t, unsigned a = 0, bool GenOptions::*m = nullptr) : name(n), attr(a), i(t), mark(m) {}
+    constexpr Opt(const char *n, std::string GenOptions::*t, const char *p, unsigned a = 0, bool GenOptions::*m = nullptr)
+        : name(n), attr(a), s(t), pick(p), mark(m) {}
+    constexpr Opt(const char *n, Setter f, unsigned a = 0) : name(n), attr(a), put(f) {}
+};
+inline bool put_coef(GenOptions &o, const std::string &v) {
+    const int c = v == "lit" ? 0 : v == "sgpr" ? 1 : v == "vgpr" ? 2 : -1;
+    if (c >= 0) o.coef_sgpr = c;
+    return c >= 0;
+}
+inline bool put_temporal(GenOptions &o, const std::string &v) {
+    const int t = v == "0" ? 0 : v == "1" ? 1 : (v == "2" || v == "force") ? 2 : -1;
+    if (t >= 0) o.temporal = t;
+    return t >= 0;
+}
+inline bool put_cc_opt(GenOptions &o, const std::string &v) { o.cc_opts.push_back(v); return true; }
 
-    bool illegal_exit = false;
-    for (int i = 1; i < argc - 1; i++) {
-        const std::string &a = arg(i);
-        auto int_opt = [&](int &dst, bool *flag) -> bool {
-            if (i != argc - 2) { dst = atoi(arg(++i).c_str()); if (flag) *flag = true; return true; }
-            res.messages += "Illegal input.\n"; res.exit_code = 255; illegal_exit = true; return false;
-        };
-        auto str_opt = [&](std::string &dst) -> bool {
-            if (i != argc - 2) { dst = arg(++i); return true; }
-            res.messages += "Illegal input.\n"; res.exit_code = 255; illegal_exit = true; return false;
-        };
-        // options that NAME the problem or the artefact; every other option is a tuning choice and switches the tuned-defaults table off
-        if (!(a == "-o" || a == "--3d" || a == "--step" || a == "--streaming" || a == "--check" || a == "--gold" || a == "--dtype" || a == "--gpus" ||
-              a == "--pair-launch" || a == "--temporal" || a == "--dist" || a == "--tuned-defaults" || a == "--out-skew" || a == "--boundary")) o.tuning_given = true;
-        if (a == "-o") { if (i != argc - 2) { o.out_name = arg(++i); o.out_set = true; } }
-        else if (a == "--3d") o.is3d = true;
-        else if (a == "--step") { if (!int_opt(o.step, nullptr)) break; }
-        else if (a == "--dist") { if (!int_opt(o.dist, nullptr)) break; }
-        else if (a == "--streaming") o.streaming = true;
-        else if (a == "--bx") { if (!int_opt(o.bx, &o.bx_set)) break; }
-        else if (a == "--by") { if (!int_opt(o.by, &o.by_set)) break; }
-        else if (a == "--sn") { if (!int_opt(o.sn, &o.sn_set)) break; }
-        else if (a == "--block-merge-x") { if (!int_opt(o.bmx, &o.mx_set)) break; }
-        else if (a == "--block-merge-y") { if (!int_opt(o.bmy, &o.my_set)) break; }
-        else if (a == "--cyclic-merge-x") { if (!int_opt(o.cmx, &o.mx_set)) break; }
-        else if (a == "--cyclic-merge-y") { if (!int_opt(o.cmy, &o.my_set)) break; }
-        else if (a == "--stream-unroll") { if (!int_opt(o.stream_unroll, nullptr)) break; }
-        else if (a == "--prefetch") o.prefetch = true;
-        else if (a == "--merge-forward") { if (!int_opt(o.merge_forward, nullptr)) break; }
-        else if (a == "--check") o.check = true;
-        else if (a == "--gold") o.gold = true;
-        // ---- additive options
-        else if (a == "--dtype") { if (!str_opt(o.dtype)) break; }
-        else if (a == "--boundary") { if (!str_opt(o.boundary)) break; }
-        else if (a == "--xrim") { if (!str_opt(o.xrim)) break; }
-        else if (a == "--schedule") { if (!str_opt(o.schedule)) break; o.schedule_set = true; }
-        else if (a == "--order") { if (!str_opt(o.order)) break; o.order_set = true; }
-        else if (a == "--pack") { if (!int_opt(o.pack, nullptr)) break; }
-        else if (a == "--row-fence") { if (!int_opt(o.row_fence, nullptr)) break; }
-        else if (a == "--out-skew") { if (!int_opt(o.out_skew, nullptr)) break; }
-        else if (a == "--gpus") { if (!int_opt(o.gpus, nullptr)) break; }
-        else if (a == "--coef") {
-            std::string v;
-            if (!str_opt(v)) break;
-            if (v == "sgpr") o.coef_sgpr = 1;
-            else if (v == "vgpr") o.coef_sgpr = 2;
-            else if (v == "lit") o.coef_sgpr = 0;
-            else { res.messages += "Illegal input.\n"; res.exit_code = 255; return res; }
+inline constexpr Opt kOptions[] = {
+    // the reference's options (main.cpp:118-230)
+    {"-o", &GenOptions::out_name, nullptr, NAMES | LOCAL, &GenOptions::out_set}, {"--3d", &GenOptions::is3d, NAMES},
+    {"--step", &GenOptions::step, NAMES}, {"--dist", &GenOptions::dist, NAMES}, {"--streaming", &GenOptions::streaming, NAMES},
+    {"--bx", &GenOptions::bx, 0, &GenOptions::bx_set}, {"--by", &GenOptions::by, 0, &GenOptions::by_set}, {"--sn", &GenOptions::sn, 0, &GenOptions::sn_set},
+    {"--block-merge-x", &GenOptions::bmx, 0, &GenOptions::mx_set}, {"--cyclic-merge-x", &GenOptions::cmx, 0, &GenOptions::mx_set},
+    {"--block-merge-y", &GenOptions::bmy, 0, &GenOptions::my_set}, {"--cyclic-merge-y", &GenOptions::cmy, 0, &GenOptions::my_set},
+    {"--stream-unroll", &GenOptions::stream_unroll}, {"--prefetch", &GenOptions::prefetch}, {"--merge-forward", &GenOptions::merge_forward},
+    {"--check", &GenOptions::check, NAMES | LOCAL}, {"--gold", &GenOptions::gold, NAMES | LOCAL},
+    // additive MI355X options
+    {"--dtype", &GenOptions::dtype, "fp32 fp64", NAMES}, {"--boundary", &GenOptions::boundary, "fixed periodic", NAMES},
+    {"--gpus", &GenOptions::gpus, NAMES | LOCAL}, {"--pair-launch", &GenOptions::pair_launch, NAMES}, {"--temporal", put_temporal, NAMES},
+    {"--out-skew", &GenOptions::out_skew, NAMES}, {"--tuned-defaults", &GenOptions::tuned_defaults, NAMES},
+    {"--schedule", &GenOptions::schedule, "scatter reuse window", 0, &GenOptions::schedule_set},
+    {"--order", &GenOptions::order, "taps rows", 0, &GenOptions::order_set}, {"--xrim", &GenOptions::xrim, "lds dpp"},
+    {"--stage", &GenOptions::stage, "reg dma"}, {"--store-mask", &GenOptions::store_mask, "branch buffer"},
+    {"--coef", put_coef}, {"--cc-opt", put_cc_opt}, {"--ref-defaults", &GenOptions::ref_defaults, SET1},
+    {"--pack", &GenOptions::pack}, {"--pin", &GenOptions::pin}, {"--row-fence", &GenOptions::row_fence}, {"--rot-mod", &GenOptions::rot_mod},
+    {"--skew", &GenOptions::skew}, {"--loader-waves", &GenOptions::loader_waves}, {"--prefetch-depth", &GenOptions::prefetch_depth},
+    {"--exact-y", &GenOptions::exact_y}, {"--exact-x", &GenOptions::exact_x}, {"--xedge-select", &GenOptions::xedge_select},
+    {"--clamp-loads", &GenOptions::clamp_loads}, {"--halo-spread", &GenOptions::halo_spread}, {"--zigzag", &GenOptions::zigzag},
+    {"--defer-stores", &GenOptions::defer_stores}, {"--drain", &GenOptions::drain}, {"--uniform-loads", &GenOptions::uniform_loads},
+    {"--lazy-rims", &GenOptions::lazy_rims}, {"--xcd-remap", &GenOptions::xcd_remap}, {"--nt-store", &GenOptions::nt_store},
+    {"--nt-load", &GenOptions::nt_load}, {"--waves-per-eu", &GenOptions::waves_per_eu}, {"--lds-pad", &GenOptions::lds_pad},
+    {"--zgroup", &GenOptions::zgroup, HIDDEN}, {"--xcd-chunk", &GenOptions::xcd_chunk, HIDDEN}, {"--prefetch-auto", &GenOptions::prefetch_auto, HIDDEN},
+    {"--debug-skip", &GenOptions::debug_skip, HIDDEN}, {"--debug-drop-barrier", &GenOptions::debug_drop_barrier, HIDDEN},
+};
+
+inline bool picks(const char *pick, const std::string &v) {
+    std::istringstream is(pick);
+    for (std::string w; is >> w;)
+        if (w == v) return true;
+    return false;
+}
+
+// One scan of args (argv[1..], the .stc path last) into res.opt, from the defaults; banner: the options as the emitted source echoes
+// them.  false: res.messages and res.exit_code say why, by the reference's rules (header comment).  A value option takes the next word
+// whatever it looks like; the last value wins.
+inline bool scan_options(const std::vector<std::string> &args, GenResult &res, std::string &banner) {
+    GenOptions &o = res.opt = GenOptions();
+    banner.clear();
+    auto illegal = [&](int code) { res.messages += "Illegal input.\n"; res.exit_code = code; return false; };
+    auto echo = [&](const std::string &w, bool slab) { banner += (banner.empty() ? "" : " ") + w; if (slab) o.slab_args.push_back(w); };
+    for (size_t i = 0, stc = args.size() - 1; i < stc; i++) {
+        const std::string &a = args[i];
+        const Opt *r = std::find_if(std::begin(kOptions), std::end(kOptions), [&](const Opt &x) { return a == x.name; });
+        if (r == std::end(kOptions)) return illegal(0);
+        if (!(r->attr & NAMES)) o.tuning_given = true;
+        const bool flag = r->b || (r->attr & SET1);
+        if (!flag && i + 1 == stc) {
+            if (a != "-o") return illegal(255);
+            echo(a, false);
+            continue;
         }
-        else if (a == "--loader-waves") { if (!int_opt(o.loader_waves, nullptr)) break; }
-        else if (a == "--rot-mod") { if (!int_opt(o.rot_mod, nullptr)) break; }
-        else if (a == "--skew") { if (!int_opt(o.skew, nullptr)) break; }
-        else if (a == "--tuned-defaults") { if (!int_opt(o.tuned_defaults, nullptr)) break; }
-        else if (a == "--pin") { if (!int_opt(o.pin, nullptr)) break; }
-        else if (a == "--exact-y") { if (!int_opt(o.exact_y, nullptr)) break; }
-        else if (a == "--exact-x") { if (!int_opt(o.exact_x, nullptr)) break; }
-        else if (a == "--xedge-select") { if (!int_opt(o.xedge_select, nullptr)) break; }
-        else if (a == "--debug-skip") { if (!int_opt(o.debug_skip, nullptr)) break; }
-        else if (a == "--debug-drop-barrier") { if (!int_opt(o.debug_drop_barrier, nullptr)) break; }
-        else if (a == "--clamp-loads") { if (!int_opt(o.clamp_loads, nullptr)) break; }
-        else if (a == "--halo-spread") { if (!int_opt(o.halo_spread, nullptr)) break; }
-        else if (a == "--zgroup") { if (!int_opt(o.zgroup, nullptr)) break; }
-        else if (a == "--xcd-chunk") { if (!int_opt(o.xcd_chunk, nullptr)) break; }
-        else if (a == "--zigzag") { if (!int_opt(o.zigzag, nullptr)) break; }
-        else if (a == "--pair-launch") { if (!int_opt(o.pair_launch, nullptr)) break; }
-        else if (a == "--prefetch-auto") { if (!int_opt(o.prefetch_auto, nullptr)) break; }
-        else if (a == "--prefetch-depth") { if (!int_opt(o.prefetch_depth, nullptr)) break; }
-        else if (a == "--temporal") {
-            std::string v;
-            if (!str_opt(v)) break;
-            if (v == "force") o.temporal = 2;
-            else if (v == "0" || v == "1" || v == "2") o.temporal = atoi(v.c_str());
-            else { res.messages += "Illegal input.\n"; res.exit_code = 255; return res; }
-        }
-        else if (a == "--defer-stores") { if (!int_opt(o.defer_stores, nullptr)) break; }
-        else if (a == "--drain") { if (!int_opt(o.drain, nullptr)) break; }
-        else if (a == "--uniform-loads") { if (!int_opt(o.uniform_loads, nullptr)) break; }
-        else if (a == "--store-mask") { if (!str_opt(o.store_mask)) break; }
-        else if (a == "--stage") { if (!str_opt(o.stage)) break; }
-        else if (a == "--cc-opt") { std::string f; if (!str_opt(f)) break; o.cc_opts.push_back(f); }
-        else if (a == "--lazy-rims") { if (!int_opt(o.lazy_rims, nullptr)) break; }
-        else if (a == "--xcd-remap") { if (!int_opt(o.xcd_remap, nullptr)) break; }
-        else if (a == "--nt-store") { if (!int_opt(o.nt_store, nullptr)) break; }
-        else if (a == "--nt-load") { if (!int_opt(o.nt_load, nullptr)) break; }
-        else if (a == "--waves-per-eu") { if (!int_opt(o.waves_per_eu, nullptr)) break; }
-        else if (a == "--lds-pad") { if (!int_opt(o.lds_pad, nullptr)) break; }
-        else if (a == "--ref-defaults") o.ref_defaults = 1;
-        else { res.messages += "Illegal input.\n"; res.exit_code = 0; return res; }
+        const std::string v = flag ? "" : args[++i];
+        if (r->b) o.*r->b = true;
+        else if (flag) o.*r->i = 1;
+        else if (r->i) o.*r->i = atoi(v.c_str());
+        else if (r->s) o.*r->s = v;
+        else if (!r->put(o, v)) return illegal(255);
+        if (r->mark) o.*r->mark = true;
+        // `--boundary fixed` is the default spelled out: it leaves no trace in the emitted source (banner and slab host alike)
+        if (a == "--boundary" && v == "fixed") continue;
+        echo(a, !(r->attr & LOCAL));
+        if (!flag) echo(v, !(r->attr & LOCAL));
     }
-    if (illegal_exit) return res;
-    if (o.dtype != "fp32" && o.dtype != "fp64") { res.messages += "Illegal input.\n"; res.exit_code = 255; return res; }
-    if (o.boundary != "fixed" && o.boundary != "periodic") { res.messages += "Illegal input.\n"; res.exit_code = 255; return res; }
+    for (const Opt &r : kOptions)
+        if (r.pick && !picks(r.pick, o.*r.s)) return illegal(255);
+    if (o.step < 1) return illegal(255);
     // an explicit --dist selects the reference's kind of reuse: `Range` source planes resident, the rest carried as partial sums
     if (!o.schedule_set && o.dist != 0) o.schedule = "reuse";
-    if (o.schedule != "scatter" && o.schedule != "window" && o.schedule != "reuse") { res.messages += "Illegal input.\n"; res.exit_code = 255; return res; }
-    if (o.order != "taps" && o.order != "rows") { res.messages += "Illegal input.\n"; res.exit_code = 255; return res; }
-    if (o.xrim != "lds" && o.xrim != "dpp") { res.messages += "Illegal input.\n"; res.exit_code = 255; return res; }
-    if (o.stage != "reg" && o.stage != "dma") { res.messages += "Illegal input.\n"; res.exit_code = 255; return res; }
-    if (o.store_mask != "buffer" && o.store_mask != "branch") { res.messages += "Illegal input.\n"; res.exit_code = 255; return res; }
-    if (o.step < 1) { res.messages += "Illegal input.\n"; res.exit_code = 255; return res; }
+    return true;
+}
 
-    const std::string &stcfile = arg(argc - 1);
+inline GenResult generate(const std::vector<std::string> &args /* argv[1..] */) {
+    GenResult res;
+    if (args.empty()) { res.messages = "Please specify the .stc file.\n"; return res; }
+    if (args[0] == "--help" || args[0] == "-h") { res.messages = std::string(help_text()) + "\n"; return res; }
+    std::string banner;
+    if (!scan_options(args, res, banner)) return res;
+    GenOptions &o = res.opt;
+
+    const std::string &stcfile = args.back();
     Stencil &st = res.st;
     st.ndim = o.is3d ? 3 : 2;
     if (st.read_stc(stcfile) != 0) { res.messages += "Error opening stencil file.\n"; res.exit_code = 255; return res; }
     // No geometry / emission option on the command line: the tuner's winner for this problem class, if it has one, supplies them
-    // (drstencil_amd/tuned_defaults.tsv).  The command is re-read with the row's options in front of the .stc, so the banner's
-    // `options:` line, the kernel info and the cache key are those of the explicit command line.
+    // (drstencil_amd/tuned_defaults.tsv).  The command is scanned again with the row's options in front of the .stc, so the banner's
+    // `options:` line, the kernel info and the cache key are those of the explicit command line.  A row holds no naming option, so the
+    // .stc as read stands.
     if (o.tuned_defaults && !o.tuning_given && !o.ref_defaults) {
-        int order = 0;
-        for (auto &e : st.pts.v) order = std::max(order, std::abs(st.ndim == 3 ? e.first.k : e.first.j));
         const char *mode = st.ndim == 3 ? "3d" : (o.streaming ? "2ds" : "2d");
         if (const TunedDefault *t = tuned_lookup(mode, tuned_shape_hash(st.pts), o.step, o.dtype, (o.temporal && o.step > 1) ? 1 : 0, st.N)) {
             std::vector<std::string> again(args.begin(), args.end() - 1);
             std::istringstream is(t->options);
             for (std::string w; is >> w;) again.push_back(w);
-            again.push_back("--tuned-defaults"); again.push_back("0");
-            again.push_back(args.back());
-            GenResult r2 = generate(again);
-            r2.tuned_from = t->options;
-            if (r2.emitted) r2.notes += std::string("drstencil: note: no geometry option given: the tuner's configuration for this stencil, step, dtype and grid size is used (") + t->options + "); --tuned-defaults 0 keeps the generic defaults\n";
-            return r2;
+            again.insert(again.end(), {"--tuned-defaults", "0", stcfile});
+            res.tuned_from = t->options;
+            if (!scan_options(again, res, banner)) return res;
         }
     }
     st.fuse(o.step);
@@ -348,18 +353,6 @@ inline GenResult generate(const std::vector<std::string> &args /* argv[1..] */) 
     res.plan = make_plan(st, o, kernel_base_name(stcfile));
     if (!res.plan.error.empty()) { res.messages += "Invalid configuration!\n"; res.exit_code = 255; return res; }
     if (!res.plan.note.empty()) res.messages += "drstencil: note: " + res.plan.note + "\n";
-    // `--boundary fixed` is the default spelled out: it leaves no trace in the emitted source (banner and slab host alike)
-    auto fixed_boundary = [&](size_t i) { return args[i] == "--boundary" && i + 2 < args.size() && args[i + 1] == "fixed"; };
-    std::string cmdline;
-    for (size_t i = 0, n = 0; i + 1 < args.size(); i++) {
-        if (fixed_boundary(i)) { i++; continue; }
-        cmdline += (n++ ? " " : "") + args[i];
-    }
-    for (size_t i = 0; i + 1 < args.size(); i++) {
-        if (args[i] == "-o" || args[i] == "--gpus" || fixed_boundary(i)) { i++; continue; }
-        if (args[i] == "--check" || args[i] == "--gold") continue;
-        o.slab_args.push_back(args[i]);
-    }
     if (o.gpus < 1 || o.gpus > 64) { res.messages += "Illegal input.\n"; res.exit_code = 255; return res; }
     if (res.plan.periodic && (o.gpus > 1 || o.pair_launch)) {
         // periodic z (y in 2D) across ranks would need a rank 0 <-> rank N-1 exchange; the pair kernel exists only for slab views
@@ -373,13 +366,16 @@ inline GenResult generate(const std::vector<std::string> &args /* argv[1..] */) 
     if (em.lds_bytes() > 160 * 1024) {   // gfx950: 160 KiB of LDS per workgroup
         res.messages += "Invalid configuration!\n"; res.exit_code = 255; res.plan.error = "tile needs more than 160 KiB of LDS"; return res;
     }
-    res.source = em.source(stcfile, cmdline);
+    res.source = em.source(stcfile, banner);
     if (res.plan.periodic) {
         const int H = st.halo;
         std::string per = st.ndim == 3 ? std::to_string(st.L - 2 * H) + " x " : "";
         per += std::to_string(st.M - 2 * H) + " x " + std::to_string(st.N - 2 * H);
         res.notes += "drstencil: note: periodic boundaries: period " + per + ", ring of width " + std::to_string(H) + " holds ghost copies\n";
     }
+    if (!res.tuned_from.empty())
+        res.notes += "drstencil: note: no geometry option given: the tuner's configuration for this stencil, step, dtype and grid size is used (" +
+                     res.tuned_from + "); --tuned-defaults 0 keeps the generic defaults\n";
     res.out_name = o.out_name;
     res.emitted = true;
     return res;

@@ -152,12 +152,13 @@ struct GenOptions {
                                  // ones, profiles/r03_sinking.md).  The pin makes each update used where it is written.  -1 auto: on with --order rows
     int gpus = 1;                // --gpus N > 1: the emitted program's main() is an N-GPU host -- launcher and ranks in one (it forks its ranks before any
                                  // HIP call, one process per GPU) on the C ABI's drs_slab_* entry points (z slabs / y slabs, RCCL send/recv halo exchange)
-    std::vector<std::string> slab_args;   // the generator options of this invocation without -o / --gpus / --check / --gold and without the .stc path
+    std::vector<std::string> slab_args;   // the generator options of this invocation without the LOCAL ones (-o / --gpus / --check / --gold of
+                                 // generator.hpp's option table), without `--boundary fixed` and without the .stc path
     int out_skew = -1;           // --out-skew <MiB>: where the output array should sit relative to the input array, modulo 64 MiB (see
                                  // HipEmitter::out_skew_bytes; -1: chosen by the generator).  It changes no kernel text: the value is published
                                  // in the info JSON / the banner and honoured by the emitted host program, which owns its allocations
     int tuned_defaults = 1;      // --tuned-defaults 0: never consult the tuner's table (generator.hpp)
-    bool tuning_given = false;   // some option other than the problem-naming ones was given
+    bool tuning_given = false;   // some option other than the problem-naming ones (NAMES in generator.hpp's option table) was given
     int skew = -1;               // -1 auto: 1 for pipelines of three or more stages (measured: fp64 3 stages 3.49 -> 3.28 ms; 2 stages lose), else 0.
                                  // --skew 1 (round 4; temporal pipelines of streaming kernels, with --prefetch): stage t consumes the plane stage t-1 completed
                                  // in the PREVIOUS iteration.  All stages of one iteration are then independent of each other: they run back to back

@@ -72,6 +72,77 @@ def test_cli_matches_reference(rec, cli_dir):
         assert rec["kernel"] in src
 
 
+# The scan's corner cases: (argv before the .stc path or after it, exit code, stdout, stderr, out.cu written, strings the source holds).
+# "k.stc" is a 64^3 7-point star (no tuned-defaults row).
+_ILL = "Illegal input.\n"
+SCAN_CASES = [
+    # the last argument is always the .stc: an earlier one is an option, here an unknown one
+    (["k.stc", "--3d"], 0, _ILL, "", False, []),
+    # a value-taking option in the second-to-last slot: 255, and the scan stops there (no second message from the post-scan checks)
+    (["--3d", "--bx", "k.stc"], 255, _ILL, "", False, []),
+    (["--3d", "--dtype", "k.stc"], 255, _ILL, "", False, []),
+    (["--3d", "--coef", "k.stc"], 255, _ILL, "", False, []),
+    (["--dtype", "bad", "--bx", "k.stc"], 255, _ILL, "", False, []),
+    # ... except -o, which is ignored there (the reference's quirk)
+    (["--3d", "-o", "k.stc"], 0, "", "", True, ["// options: --3d -o\n"]),
+    # an unknown option: exit 0 at once, even before a later error
+    (["--bogus", "k.stc"], 0, _ILL, "", False, []),
+    (["--3d", "--bogus", "--bx", "k.stc"], 0, _ILL, "", False, []),
+    # a bad --coef / --temporal value fails where the scan meets it
+    (["--coef", "bad", "--bogus", "k.stc"], 255, _ILL, "", False, []),
+    (["--temporal", "bad", "--bogus", "k.stc"], 255, _ILL, "", False, []),
+    # the other value sets and --step >= 1 are checked after the scan
+    *[c for opt, bad in (("--dtype", "bad"), ("--boundary", "bad"), ("--schedule", "bad"), ("--order", "bad"), ("--xrim", "bad"),
+                         ("--stage", "bad"), ("--store-mask", "bad"), ("--step", "0"))
+      for c in (([opt, bad, "--bogus", "k.stc"], 0, _ILL, "", False, []), (["--3d", opt, bad, "k.stc"], 255, _ILL, "", False, []))],
+    # a value option takes the next word even when it looks like an option: bx = atoi("--3d") = 0
+    (["--3d", "--bx", "--3d", "k.stc"], 255, "Invalid configuration!\n", "drstencil: workgroup must have 1..1024 threads\n", False, []),
+    # the last value wins; --cc-opt accumulates
+    (["--3d", "--bx", "16", "--bx", "32", "k.stc"], 0, "", "", True, ["#define Bx 32\n"]),
+    (["--3d", "--coef", "sgpr", "--coef", "lit", "--dtype", "fp32", "--dtype", "fp64", "k.stc"], 0, "", "", True, ['\\"dtype\\":\\"fp64\\"']),
+    (["--3d", "--cc-opt", "-fno-slp-vectorize", "--cc-opt", "-fno-unroll-loops", "k.stc"], 0, "", "", True,
+     ["-ffp-contract=off -fno-slp-vectorize -fno-unroll-loops -Rpass"]),
+    # an explicit --dist without --schedule selects reuse
+    (["--3d", "--dist", "1", "k.stc"], 0, "", "", True, ['\\"schedule\\":\\"reuse\\"']),
+    (["--3d", "--dist", "1", "--schedule", "scatter", "k.stc"], 0, "", "", True, ['\\"schedule\\":\\"scatter\\"']),
+    # the banner's options line and the slab host's options: --boundary fixed leaves no trace; the slab host drops --gpus / --check
+    (["--3d", "--gpus", "2", "--boundary", "fixed", "--check", "k.stc"], 0, "", "", True,
+     ["// options: --3d --gpus 2 --check\n", 'drs_opts[] = { "--3d", NULL }']),
+    (["--3d", "--boundary", "periodic", "--check", "--gpus", "1", "k.stc"], 0, "",
+     "drstencil: note: periodic boundaries: period 62 x 62 x 62, ring of width 1 holds ghost copies\n", True,
+     ["// options: --3d --boundary periodic --check --gpus 1\n"]),
+]
+
+
+@pytest.mark.parametrize("args,rc,stdout,stderr,written,has", SCAN_CASES, ids=[" ".join(c[0]) for c in SCAN_CASES])
+def test_cli_scan_corner_cases(args, rc, stdout, stderr, written, has, tmp_path):
+    write_stc(str(tmp_path / "k.stc"), 3, (64, 64, 64), 4, _mg().STAR3)
+    p = subprocess.run([CLI] + args, cwd=str(tmp_path), capture_output=True, text=True)
+    assert (p.returncode, p.stdout, p.stderr) == (rc, stdout, stderr)
+    out = tmp_path / "out.cu"
+    assert out.exists() == written
+    for s in has:
+        assert s in out.read_text(), s
+
+
+def test_option_table_and_help_agree(tmp_path):
+    """The generator's option table and its hand-written help text name the same options: every row that is not HIDDEN begins a help
+    line, and every option that begins a help line has a row (--help / -h excepted: they are handled before the scan, and only as the
+    first argument)."""
+    import re
+    exe = str(tmp_path / "option_table")
+    subprocess.check_call(["g++", "-std=c++17", "-I", os.path.join(ROOT, "drstencil_amd", "csrc"), os.path.join(ROOT, "tests", "native", "option_table.cpp"), "-o", exe])
+    rows = [ln.split() for ln in subprocess.run([exe], capture_output=True, text=True, check=True).stdout.splitlines()]
+    names = [r[0] for r in rows]
+    assert len(names) == len(set(names)) and "--3d" in names and "--debug-skip" in names
+    shown = {r[0] for r in rows if len(r) == 1}
+    help_text = subprocess.run([CLI, "--help"], capture_output=True, text=True, check=True).stdout
+    leading = {m.group(1) for m in re.finditer(r"^(--?[a-z0-9][a-z0-9-]*)", help_text, re.M)} - {"--help"}
+    assert shown - leading == set(), "table options without a help line (or not marked HIDDEN)"
+    assert leading - set(names) == set(), "help lines for options the table does not have"
+    assert leading - shown == set(), "HIDDEN options with a help line"
+
+
 def test_partition_table_from_survey():
     """(step, dist) -> Halo, Range, fk/fj/fi/bw."""
     b = os.path.join(ROOT, "benchmarks")
