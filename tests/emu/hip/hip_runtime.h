@@ -2,7 +2,8 @@
 // emitted by drstencil can be executed on the host (no GPU in the authoring container).
 // Every GPU thread of a workgroup is a ucontext fiber; __syncthreads() yields to a
 // round-robin scheduler, so barrier semantics are exact and runs are deterministic.
-// Workgroups run one after another.  Used only by tests/test_emulated_kernels.py.
+// Workgroups run one after another.  Used through tests/emu_util.py by tests/test_emulated_kernels.py,
+// tests/test_periodic_cpu.py and tests/test_memory_footprint_cpu.py (there in child processes, on guarded arrays).
 #pragma once
 #include <ucontext.h>
 
