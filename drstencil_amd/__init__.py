@@ -225,6 +225,12 @@ class Kernel:
         """True for kernels generated with --boundary periodic: every launch first fills the input's ring from its interior (wrap())."""
         return self.info.get("boundary") == "periodic"
 
+    @property
+    def time_order(self):
+        """2 for kernels generated with --time-order 2: a launch computes out = S(in) - out_old on the interior, so the output array's
+        interior is input too (the ping-pong loop of run() is then the leapfrog scheme u(t+1) = S(u(t)) - u(t-1)); else 1."""
+        return int(self.info.get("time_order", 1))
+
     def wrap(self, d, stream=0):
         """--boundary periodic: fill the ring of width Halo of the device array `d` with the periodic images of its interior (period
         dim - 2 Halo per dimension), asynchronously on `stream`.  Every launch does this to its input first."""
@@ -299,11 +305,13 @@ class Kernel:
     def bytes_per_launch(self):
         i = self.info
         pts = i["M"] * i["N"] * (i["L"] if i["ndim"] == 3 else 1)
-        return 2 * (4 if i["dtype"] == "fp32" else 8) * pts
+        # --time-order 2 also reads the old output: two reads and one write per point is the algorithmic minimum
+        return (3 if self.time_order == 2 else 2) * (4 if i["dtype"] == "fp32" else 8) * pts
 
     # ---- placement of the output array (csrc/emit_hip.hpp: out_skew_bytes; profiles/r03_probe_skew4.log) ----
     def array_bytes(self):
-        return self.bytes_per_launch() // 2
+        i = self.info
+        return (4 if i["dtype"] == "fp32" else 8) * i["M"] * i["N"] * (i["L"] if i["ndim"] == 3 else 1)
 
     def pair_layout(self, skew=None):
         """(arena bytes, byte offset of the output array) for both arrays of this kernel in ONE allocation: the output starts

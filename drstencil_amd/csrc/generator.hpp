@@ -110,6 +110,12 @@ MI355X options:
                         launch (in -> out) first refills in's ring from in's interior -- it OVERWRITES the input array's ring --
                         then sweeps as with fixed; out's ring is not touched.  Needs every dimension >= 3 * Halo; not with
                         --gpus N > 1 or --pair-launch 1.
+--time-order <1|2>      1 (default): out = S(in), a first-order update.  2: out = S(in) - out_old on the interior, the leapfrog
+                        update of a second-order equation (wave equation: u(t+1) = S(u(t)) - u(t-1), the factor 2 of 2u folded
+                        into the centre coefficient).  The ping-pong loop k(A,B); k(B,A) is then leapfrog as it stands: the
+                        OUTPUT array's interior is input too (its ring is neither read nor written).  S(in) is the same FMA chain,
+                        rounded once; the subtraction is one more rounded operation.  Needs --step 1; not with --temporal,
+                        --gpus N > 1 or --pair-launch 1.
 --xrim <lds|dpp>        x halo inside a wavefront by DPP wave shifts (default) or through LDS.
 --schedule <scatter|reuse|window>  How reuse along the streamed dimension is split between source planes kept on chip and
                         partial sums carried in VGPRs (results never depend on it):
@@ -245,6 +251,7 @@ inline constexpr Opt kOptions[] = {
     {"--check", &GenOptions::check, NAMES | LOCAL}, {"--gold", &GenOptions::gold, NAMES | LOCAL},
     // additive MI355X options
     {"--dtype", &GenOptions::dtype, "fp32 fp64", NAMES}, {"--boundary", &GenOptions::boundary, "fixed periodic", NAMES},
+    {"--time-order", &GenOptions::time_order, NAMES},
     {"--gpus", &GenOptions::gpus, NAMES | LOCAL}, {"--pair-launch", &GenOptions::pair_launch, NAMES}, {"--temporal", put_temporal, NAMES},
     {"--out-skew", &GenOptions::out_skew, NAMES}, {"--tuned-defaults", &GenOptions::tuned_defaults, NAMES},
     {"--schedule", &GenOptions::schedule, "scatter reuse window", 0, &GenOptions::schedule_set},
@@ -297,12 +304,14 @@ inline bool scan_options(const std::vector<std::string> &args, GenResult &res, s
         if (r->mark) o.*r->mark = true;
         // `--boundary fixed` is the default spelled out: it leaves no trace in the emitted source (banner and slab host alike)
         if (a == "--boundary" && v == "fixed") continue;
+        if (a == "--time-order" && o.time_order == 1) continue;       // likewise
         echo(a, !(r->attr & LOCAL));
         if (!flag) echo(v, !(r->attr & LOCAL));
     }
     for (const Opt &r : kOptions)
         if (r.pick && !picks(r.pick, o.*r.s)) return illegal(255);
     if (o.step < 1) return illegal(255);
+    if (o.time_order != 1 && o.time_order != 2) return illegal(255);
     // an explicit --dist selects the reference's kind of reuse: `Range` source planes resident, the rest carried as partial sums
     if (!o.schedule_set && o.dist != 0) o.schedule = "reuse";
     return true;
@@ -361,6 +370,13 @@ inline GenResult generate(const std::vector<std::string> &args /* argv[1..] */) 
                                     : "--boundary periodic cannot be combined with --pair-launch 1 (the pair kernel serves the slab runtime, which has no periodic exchange)";
         return res;
     }
+    if (res.plan.second_order && (o.gpus > 1 || o.pair_launch)) {
+        // a slab's ghost planes are recomputed redundantly under every = 2: they would need valid old values too; the pair kernel serves the slabs
+        res.messages += "Invalid configuration!\n"; res.exit_code = 255;
+        res.plan.error = o.gpus > 1 ? "--time-order 2 cannot be combined with --gpus N > 1 (the slab runtime keeps no old values in its ghost planes)"
+                                    : "--time-order 2 cannot be combined with --pair-launch 1 (the pair kernel serves the slab runtime, which has no second-order form)";
+        return res;
+    }
     HipEmitter em(res.plan, o);
     if (!em.config_error().empty()) { res.messages += "Invalid configuration!\n"; res.exit_code = 255; res.plan.error = em.config_error(); return res; }
     if (em.lds_bytes() > 160 * 1024) {   // gfx950: 160 KiB of LDS per workgroup
@@ -373,6 +389,8 @@ inline GenResult generate(const std::vector<std::string> &args /* argv[1..] */) 
         per += std::to_string(st.M - 2 * H) + " x " + std::to_string(st.N - 2 * H);
         res.notes += "drstencil: note: periodic boundaries: period " + per + ", ring of width " + std::to_string(H) + " holds ghost copies\n";
     }
+    if (res.plan.second_order)
+        res.notes += "drstencil: note: second-order time stepping: a launch computes out = S(in) - out_old on the interior (the output array's interior is input)\n";
     if (!res.tuned_from.empty())
         res.notes += "drstencil: note: no geometry option given: the tuner's configuration for this stencil, step, dtype and grid size is used (" +
                      res.tuned_from + "); --tuned-defaults 0 keeps the generic defaults\n";

@@ -170,6 +170,9 @@ struct GenOptions {
     std::string boundary = "fixed";   // --boundary fixed: the ring of width Halo is frozen input (the reference's Dirichlet boundary);
                                  // periodic: the ring holds ghost copies of the interior, refilled from the input's interior by wrap_<name> at the
                                  // start of every launch (period dim - 2 Halo per dimension).  It names the problem, not a tuning choice
+    int time_order = 1;          // --time-order 2: a launch computes out = S(in) - out_old on the interior (the leapfrog update of a second-order
+                                 // equation, u(t+1) = S(u(t)) - u(t-1): the ping-pong loop k(A,B); k(B,A) is then leapfrog as it stands).  The old
+                                 // output is a third memory stream of the sweep, read once.  It names the problem, not a tuning choice
 };
 
 struct Tap {
@@ -220,6 +223,7 @@ struct KernelPlan {
     double drift_per_launch = 0.0;   // the same after one launch (grows ~ launches^0.62)
     int horizon_iterations = -1;     // largest `iterations` for which the estimate stays within the bar (-1: unlimited, gold order)
     bool periodic = false;   // --boundary periodic: every launch first fills the input's ring from its interior (wrap_<name>)
+    bool second_order = false;   // --time-order 2: out = S(in) - out_old on the interior (out's interior is input, each cell's old value reaching only that cell)
     std::string error;       // non-empty: invalid configuration
     std::string note;        // non-empty: something the user asked for was not done (printed by the generator, kept in the banner)
 };

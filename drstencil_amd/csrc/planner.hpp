@@ -270,6 +270,11 @@ inline KernelPlan make_plan(const Stencil &st, const GenOptions &o_in, const std
     p.periodic = (o.boundary == "periodic");
     if (p.periodic && (st.N < 3 * H || st.M < 3 * H || (st.ndim == 3 && st.L < 3 * H))) { p.error = "--boundary periodic needs every dimension >= 3 * Halo (period >= Halo)"; return p; }
 
+    // --time-order 2: one launch is one leapfrog step.  A fused S^n minus out_old is not n leapfrog steps, and on-chip stages are that too
+    p.second_order = (o.time_order == 2);
+    if (p.second_order && o_in.step > 1) { p.error = "--time-order 2 needs --step 1 (a fused S^n minus the old output is not n leapfrog steps)"; return p; }
+    if (p.second_order && o_in.temporal) { p.error = "--time-order 2 cannot be combined with --temporal (on-chip stages fuse time steps; leapfrog needs the old output of every step)"; return p; }
+
     if (o.loader_waves > 0 && o.stage != "dma") { p.error = "--loader-waves goes with --stage dma"; return p; }
     if (o.stage == "dma") {
         // LDS-DMA writes 64 lanes x 16 bytes of one wavefront instruction to consecutive LDS addresses: the LDS image is

@@ -44,6 +44,14 @@ def refuse_periodic(opts, who):
                          "rank 0 <-> rank R-1 exchange); run it on one GPU" % who)
 
 
+def refuse_second_order(opts, who):
+    """--time-order 2 has no slab form: under every = 2 the ghost planes are recomputed redundantly and would need valid old values."""
+    opts = list(opts or ())
+    if any(a == "--time-order" and i + 1 < len(opts) and opts[i + 1] == "2" for i, a in enumerate(opts)):
+        raise ValueError("%s: --time-order 2 is not supported by the slab decomposition (redundantly computed ghost planes would need "
+                         "valid old values); run it on one GPU" % who)
+
+
 def slab_bounds(L, world, rank):
     """Planes [z0, z1) owned by `rank` (balanced split of the outermost dim)."""
     return (rank * L) // world, ((rank + 1) * L) // world
@@ -287,6 +295,8 @@ class HipSweep:
         keep the RCCL send/recv kernel off the CUs."""
         refuse_periodic(opts, "HipSweep")
         refuse_periodic(alone_opts, "HipSweep")
+        refuse_second_order(opts, "HipSweep")
+        refuse_second_order(alone_opts, "HipSweep")
         self.base_stc, self.opts, self.cache_dir = base_stc, list(opts), cache_dir
         self.alone_opts = list(alone_opts) if alone_opts else None
         self.ndim = 3 if "--3d" in self.opts else 2
@@ -400,6 +410,7 @@ class SlabRun:
         """dims = (L, M, N) for a 3D run cut along z, or (M, N) for a 2D run cut along y; every = launches per
         exchange (1 or 2, see SlabPlan)."""
         refuse_periodic(getattr(sweep, "opts", None), "SlabRun")
+        refuse_second_order(getattr(sweep, "opts", None), "SlabRun")
         self.torch, self.dist = torch, dist
         dims = tuple(dims)
         self.plan = SlabPlan(dims[0], H, world, rank, every if world > 1 else 1)
@@ -590,6 +601,8 @@ class NativeSlabRun:
                  rehearse_world=0, cache_dir=None):
         refuse_periodic(opts, "NativeSlabRun")
         refuse_periodic(alone_opts, "NativeSlabRun")
+        refuse_second_order(opts, "NativeSlabRun")
+        refuse_second_order(alone_opts, "NativeSlabRun")
         self.torch, self.dist = torch, dist
         dims = tuple(dims)
         pworld = rehearse_world or world

@@ -64,7 +64,8 @@ int drs_kernel_unload(drs_kernel *k);
  *                                  largest iteration count for which it does, and "temporal_forced": 1 marks --temporal force.
  *   "out_skew_bytes", "placement_period_bytes": where the output array should sit relative to the input array, modulo the period
  *                                  (64 MiB): see drs_kernel_pair_layout below.
- *   "boundary": "periodic", "period": [P...]   only for kernels generated with --boundary periodic (see drs_kernel_wrap). */
+ *   "boundary": "periodic", "period": [P...]   only for kernels generated with --boundary periodic (see drs_kernel_wrap).
+ *   "time_order": 2                only for kernels generated with --time-order 2 (see drs_kernel_launch). */
 const char *drs_kernel_info(const drs_kernel *k);
 const char *drs_kernel_path(const drs_kernel *k);   /* the loaded shared object */
 /* JSON: vgprs, agprs, sgprs, scratch_bytes_per_lane, sgpr_spill, vgpr_spill, occupancy_waves_per_simd, lds_bytes of
@@ -85,7 +86,11 @@ int drs_kernel_pair_layout(const drs_kernel *k, size_t *arena_bytes, size_t *out
 /* one launch of dr_<name><<<grid, block, 0, stream>>>(in, out): codegen.hpp:577,582-583.
  * --boundary periodic kernels first run wrap_<name> on d_in (drs_kernel_wrap), so d_in's RING IS OVERWRITTEN although the
  * parameter is const; the result depends only on d_in's interior, and d_out's ring is not touched.  The same holds for
- * drs_kernel_launch_gold, drs_kernel_run and drs_kernel_run_timed, whose launches go through the same entry points. */
+ * drs_kernel_launch_gold, drs_kernel_run and drs_kernel_run_timed, whose launches go through the same entry points.
+ * --time-order 2 kernels compute d_out = S(d_in) - d_out on the interior: d_out's INTERIOR IS INPUT (each cell's old value reaches
+ * only that cell; d_out's ring is neither read nor written).  The ping-pong loop of drs_kernel_run is then the leapfrog scheme
+ * u(t+1) = S(u(t)) - u(t-1) with d_a = u(t), d_b = u(t-1); the same holds for drs_kernel_launch_gold.  Such kernels need --step 1;
+ * --temporal, --gpus N > 1, --pair-launch 1 and the drs_slab_* runtime refuse them. */
 int drs_kernel_launch(drs_kernel *k, const void *d_in, void *d_out, void *stream);
 /* one launch of dr2_<name>: the same sweep over TWO (in, out) pairs (kernels generated with --pair-launch 1; -2 otherwise).
  * No reference counterpart: the two boundary views of a slab-decomposed run (drstencil_amd/multigpu.py) in one launch. */
@@ -106,7 +111,8 @@ int drs_kernel_wrap(drs_kernel *k, void *d, void *stream);
  * that was not built with --temporal force: build the fused kernel for such a run.  Asynchronous on `stream`. */
 int drs_kernel_run(drs_kernel *k, void *d_a, void *d_b, int iterations, int gold, void *stream);
 /* `warmup` untimed launches (A,B) (codegen.hpp:575-578), then the loop above bracketed by
- * HIP events recorded on `stream`; blocks until done; *ms = elapsed milliseconds. */
+ * HIP events recorded on `stream`; blocks until done; *ms = elapsed milliseconds.  With a --time-order 2 kernel the warm-up
+ * launches ADVANCE THE STATE (each reads and rewrites d_b's interior): restore both arrays afterwards if the values matter. */
 int drs_kernel_run_timed(drs_kernel *k, void *d_a, void *d_b, int iterations, int warmup, void *stream, float *ms);
 
 /* ---- N > 1: one rank of a slab-decomposed run (z slabs in 3D, y slabs in 2D), one process per GPU -----------------------------
