@@ -308,7 +308,7 @@ class Kernel:
         # --time-order 2 also reads the old output: two reads and one write per point is the algorithmic minimum
         return (3 if self.time_order == 2 else 2) * (4 if i["dtype"] == "fp32" else 8) * pts
 
-    # ---- placement of the output array (csrc/emit_hip.hpp: out_skew_bytes; profiles/r03_probe_skew4.log) ----
+    # ---- placement of the output array (csrc/schedule.hpp: Schedule::out_skew_bytes; profiles/r03_probe_skew4.log) ----
     def array_bytes(self):
         i = self.info
         return (4 if i["dtype"] == "fp32" else 8) * i["M"] * i["N"] * (i["L"] if i["ndim"] == 3 else 1)

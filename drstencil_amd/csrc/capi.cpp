@@ -232,7 +232,7 @@ drs_kernel *drs_kernel_build(int argc, const char *const *argv, const char *cach
     if (log) *log = nullptr;
     GenResult r = generate(to_args(argc, argv));
     if (!r.emitted) {
-        if (log) *log = dup_cstr(r.messages + r.notes + (r.plan.error.empty() ? "" : ("drstencil: " + r.plan.error + "\n")));
+        if (log) *log = dup_cstr(r.messages + r.notes + (r.error.empty() ? "" : ("drstencil: " + r.error + "\n")));
         return nullptr;
     }
     const std::string here = self_dir();

@@ -49,7 +49,8 @@ struct GenResult {
     std::string out_name;
     bool emitted = false;
     Stencil st;
-    KernelPlan plan;
+    KernelPlan plan;        // as make_plan() returned it: nobody writes to it afterwards
+    std::string error;      // non-empty: why the configuration is invalid (the planner's reason, the schedule's or the generator's own)
     GenOptions opt;
     std::string notes;        // what the command prints on STDERR: remarks the reference has no counterpart for on a reference command line (stdout stays the reference's)
     std::string tuned_from;   // non-empty: the geometry / emission options came from the tuned-defaults table (this row's option string)
@@ -360,29 +361,29 @@ inline GenResult generate(const std::vector<std::string> &args /* argv[1..] */) 
         if (o.pack < 0) o.pack = 0;       // packed pairs buy nothing with four waves per SIMD
     }
     res.plan = make_plan(st, o, kernel_base_name(stcfile));
-    if (!res.plan.error.empty()) { res.messages += "Invalid configuration!\n"; res.exit_code = 255; return res; }
+    if (!res.plan.error.empty()) { res.messages += "Invalid configuration!\n"; res.exit_code = 255; res.error = res.plan.error; return res; }
     if (!res.plan.note.empty()) res.messages += "drstencil: note: " + res.plan.note + "\n";
     if (o.gpus < 1 || o.gpus > 64) { res.messages += "Illegal input.\n"; res.exit_code = 255; return res; }
     if (res.plan.periodic && (o.gpus > 1 || o.pair_launch)) {
         // periodic z (y in 2D) across ranks would need a rank 0 <-> rank N-1 exchange; the pair kernel exists only for slab views
         res.messages += "Invalid configuration!\n"; res.exit_code = 255;
-        res.plan.error = o.gpus > 1 ? "--boundary periodic cannot be combined with --gpus N > 1 (the slab runtime has no periodic exchange)"
+        res.error = o.gpus > 1 ? "--boundary periodic cannot be combined with --gpus N > 1 (the slab runtime has no periodic exchange)"
                                     : "--boundary periodic cannot be combined with --pair-launch 1 (the pair kernel serves the slab runtime, which has no periodic exchange)";
         return res;
     }
     if (res.plan.second_order && (o.gpus > 1 || o.pair_launch)) {
         // a slab's ghost planes are recomputed redundantly under every = 2: they would need valid old values too; the pair kernel serves the slabs
         res.messages += "Invalid configuration!\n"; res.exit_code = 255;
-        res.plan.error = o.gpus > 1 ? "--time-order 2 cannot be combined with --gpus N > 1 (the slab runtime keeps no old values in its ghost planes)"
+        res.error = o.gpus > 1 ? "--time-order 2 cannot be combined with --gpus N > 1 (the slab runtime keeps no old values in its ghost planes)"
                                     : "--time-order 2 cannot be combined with --pair-launch 1 (the pair kernel serves the slab runtime, which has no second-order form)";
         return res;
     }
-    HipEmitter em(res.plan, o);
-    if (!em.config_error().empty()) { res.messages += "Invalid configuration!\n"; res.exit_code = 255; res.plan.error = em.config_error(); return res; }
-    if (em.lds_bytes() > 160 * 1024) {   // gfx950: 160 KiB of LDS per workgroup
-        res.messages += "Invalid configuration!\n"; res.exit_code = 255; res.plan.error = "tile needs more than 160 KiB of LDS"; return res;
+    const Schedule sched(res.plan, o);
+    if (!sched.config_error().empty()) { res.messages += "Invalid configuration!\n"; res.exit_code = 255; res.error = sched.config_error(); return res; }
+    if (sched.lds_bytes() > 160 * 1024) {   // gfx950: 160 KiB of LDS per workgroup
+        res.messages += "Invalid configuration!\n"; res.exit_code = 255; res.error = "tile needs more than 160 KiB of LDS"; return res;
     }
-    res.source = em.source(stcfile, banner);
+    res.source = HipEmitter(sched).source(stcfile, banner);
     if (res.plan.periodic) {
         const int H = st.halo;
         std::string per = st.ndim == 3 ? std::to_string(st.L - 2 * H) + " x " : "";

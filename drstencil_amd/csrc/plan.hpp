@@ -22,7 +22,7 @@
 //                       planes the reference keeps in shared memory, the rest of the reuse going through partial sums in
 //                       `out` (atomicAdd).  Here an explicit --dist selects --schedule reuse: `Range` planes stay resident in
 //                       register windows and partial sums are carried in VGPRs over the other R - Range planes
-//                       (emit_hip.hpp: carry()); without --dist everything is carried (scatter).  Different legal --dist
+//                       (schedule.hpp: carry()); without --dist everything is carried (scatter).  Different legal --dist
 //                       values give different kernels and identical results.
 //   --merge-forward t   reference: forward sets smaller than t are folded back into the backward set.  Here, per retained
 //                       plane: fewer in-plane taps than t -> its neighbours are re-read from LDS when due ("folded into the
@@ -155,7 +155,7 @@ struct GenOptions {
     std::vector<std::string> slab_args;   // the generator options of this invocation without the LOCAL ones (-o / --gpus / --check / --gold of
                                  // generator.hpp's option table), without `--boundary fixed` and without the .stc path
     int out_skew = -1;           // --out-skew <MiB>: where the output array should sit relative to the input array, modulo 64 MiB (see
-                                 // HipEmitter::out_skew_bytes; -1: chosen by the generator).  It changes no kernel text: the value is published
+                                 // Schedule::out_skew_bytes; -1: chosen by the generator).  It changes no kernel text: the value is published
                                  // in the info JSON / the banner and honoured by the emitted host program, which owns its allocations
     int tuned_defaults = 1;      // --tuned-defaults 0: never consult the tuner's table (generator.hpp)
     bool tuning_given = false;   // some option other than the problem-naming ones (NAMES in generator.hpp's option table) was given
@@ -210,12 +210,10 @@ struct KernelPlan {
     int OY = 1;              // rows owned (stored) per tile
     int NBX = 1, NBY = 1, NBS = 1;
     int NT = 256;
-    int SROW = 0, SROWS = 0, NSLOT = 2;  // LDS row length, rows per plane, plane slots
-    int UN = 1;              // unroll of the streaming loop
-    bool prefetch = false;
-    int PD = 1;              // prefetch depth (planes in flight)
-    int ws = 0;              // loader wavefronts (--loader-waves): planes are requested by them, DEPTH = PD planes ahead, into NSLOT = PD + 1 slots
-    bool dma = false;        // --stage dma: planes are staged by LDS-DMA into a per-lane-dense LDS image (emit_hip.hpp)
+    int SROW_MIN = 0, SROWS = 0;         // LDS row length before it is rounded up to whole vectors (Schedule::SROW), rows per plane
+    bool prefetch = false;   // (slots, depth and unroll follow from the schedule: Schedule::NSLOT, PD, UN)
+    int ws = 0;              // loader wavefronts (--loader-waves): planes are requested by them, PD planes ahead, into a ring of PD + 1 slots
+    bool dma = false;        // --stage dma: planes are staged by LDS-DMA into a per-lane-dense LDS image (schedule.hpp)
     // temporal blocking and the tolerance (planner.hpp: temporal_drift): which arithmetic the kernel computes
     bool reassociated = false;   // true: on-chip stages (equal to the reference's fused arithmetic up to rounding); false: gold order, bit-exact
     bool temporal_forced = false;    // --temporal force: emitted although the estimate may exceed the bar

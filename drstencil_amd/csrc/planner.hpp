@@ -148,7 +148,7 @@ inline KernelPlan make_plan(const Stencil &st, const GenOptions &o_in, const std
     // Fused multi-step kernels in 3D (step > 1 without --temporal; tuned on 3d7pt_star 1024^3 step 2,
     // profiles/r01_tune_c4_s2_exhaustive.txt, r01_tune_c3_s2_depth_exhaustive.txt): the wide fused window costs
     // registers, so 2 rows per lane, 512 lanes (fp32: 32 x 16, the optimum of both searches; fp64: 64 x 8), longer
-    // stream blocks (the z halo is step*order planes) and software prefetch (depth: see HipEmitter::analyse).
+    // stream blocks (the z halo is step*order planes) and software prefetch (depth: see Schedule::analyse).
     if (!o.ref_defaults && !o.temporal && st.step > 1 && st.ndim == 3) {
         // beyond the 25-point fused 7-point star (63-point step 3, 27-point fused cross, ...) the partial sums and rims of
         // a 512-lane workgroup no longer fit 256 registers per lane and spill to scratch: 256 lanes (64 x 4) may use the
@@ -278,7 +278,7 @@ inline KernelPlan make_plan(const Stencil &st, const GenOptions &o_in, const std
     if (o.loader_waves > 0 && o.stage != "dma") { p.error = "--loader-waves goes with --stage dma"; return p; }
     if (o.stage == "dma") {
         // LDS-DMA writes 64 lanes x 16 bytes of one wavefront instruction to consecutive LDS addresses: the LDS image is
-        // dense per (row, vector, lane) and the halo pieces dense per loader task (emit_hip.hpp); what that needs:
+        // dense per (row, vector, lane) and the halo pieces dense per loader task (schedule.hpp); what that needs:
         if (!p.has_s) { p.error = "--stage dma is for streaming kernels"; return p; }
         if (p.stages > 1) { p.error = "--stage dma: on-chip stages exchange through LDS writes"; return p; }
         if (p.VL * (p.fp32 ? 4 : 8) != 16) { p.error = "--stage dma needs 16-byte vectors (N and the x merge factor multiples of 4 fp32 / 2 fp64)"; return p; }
@@ -296,9 +296,8 @@ inline KernelPlan make_plan(const Stencil &st, const GenOptions &o_in, const std
             p.ws = o.loader_waves;
         }
     }
-    p.SROW = p.PADL + p.TX + p.PADR + o.lds_pad;
+    p.SROW_MIN = p.PADL + p.TX + p.PADR + o.lds_pad;
     p.SROWS = p.has_y ? p.TY + p.hym + p.hyp : 1;
-    if (p.stages > 1) p.NSLOT = p.stages;
     return p;
 }
 

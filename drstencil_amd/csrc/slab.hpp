@@ -186,7 +186,7 @@ drs_slab *drs_slab_open(int argc, const char *const *argv, int alone_argc, const
     const std::string base_stc = args.back();
     args.pop_back();
     GenResult r = generate(to_args(argc, argv));
-    if (!r.emitted) return fail(r.messages + (r.plan.error.empty() ? "" : ("drstencil: " + r.plan.error)));
+    if (!r.emitted) return fail(r.messages + (r.error.empty() ? "" : ("drstencil: " + r.error)));
     if (r.plan.second_order) return fail("drs_slab_open: --time-order 2 is not supported by the slab runtime (redundantly computed ghost planes would need valid old values)");
     if (r.plan.periodic) return fail("drs_slab_open: --boundary periodic is not supported by the slab runtime (periodic slabs need a rank 0 <-> rank N-1 exchange)");
     drs_slab *s = new drs_slab();

@@ -333,7 +333,7 @@ class HipSweep:
 
 
 
-PLACEMENT_PERIOD = 64 << 20      # csrc/emit_hip.hpp: kPlacementPeriod
+PLACEMENT_PERIOD = 64 << 20      # csrc/schedule.hpp: Schedule::kPlacementPeriod
 
 
 def slab_pair(torch, shape, dtype, device, skew=None):

@@ -1,0 +1,235 @@
+#!/usr/bin/env python3
+"""emit_corpus.py OUTDIR [--lib libdrstencil_amd.so] [--cli drstencil] -- what the generator emits, pinned byte for byte.
+
+For every argument list of the corpus one file OUTDIR/<nnnn>.txt: the list, the exit code, the messages (stdout + notes, as
+drs_generate returns them), for a rejected list what the command prints on stderr, and the emitted source.  OUTDIR/MANIFEST has one
+line per list: sha256 of that file, its number, the list.  Two generators emit the same text for the whole corpus iff `diff -r` of
+their OUTDIRs is empty.  Nothing is compiled and no GPU is needed.
+
+--lib / --cli name the generator under test (default: this tree's); the argument lists, and so the spec paths in the banners, always
+come from THIS tree, so whole files compare equal.  To compare with another commit:
+
+    git worktree add /tmp/parent HEAD~1 && make -C /tmp/parent/drstencil_amd/csrc
+    scripts/emit_corpus.py /tmp/a --lib /tmp/parent/drstencil_amd/libdrstencil_amd.so --cli /tmp/parent/bin/drstencil
+    scripts/emit_corpus.py /tmp/b && diff -r /tmp/a /tmp/b
+
+The corpus: everything __graft_entry__.build() emits without a slab-view spec written into the cache; a seeded sample of the tuner's
+r3 and r4 spaces; the host-program variants; one list per value of every option that selects an emitter
+branch.  --coverage prints, per such option value, how many lists of the corpus carry it.
+"""
+import argparse
+import ctypes
+import hashlib
+import os
+import random
+import subprocess
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+STC = os.path.join(ROOT, "tests", "stc")
+
+
+def stc(name):
+    return os.path.join(STC, name + ".stc")
+
+
+def build_lists():
+    """The argument lists __graft_entry__.build() hands to the generator (those that need no spec written into the cache), as
+    (cwd or None, list)."""
+    from gpu_cases import all_build_args, golden_args, fuzz_sample_jobs
+    from helpers import golden_cases, load_golden
+    import bench
+    import periodic_cases
+    import wave_cases
+    jobs = all_build_args()
+    for c in golden_cases():
+        meta = load_golden(c)[0]
+        for rows in (False, True):
+            opts, path = golden_args(c, meta, rows=rows)
+            jobs.append(opts + [path])
+    jobs += bench.kernel_arg_sets() + periodic_cases.all_build_args() + wave_cases.all_build_args()
+    jobs += [j[3] for j in fuzz_sample_jobs()]
+    for xrim in ("lds", "dpp"):
+        jobs.append(["--dtype", "fp32", "--streaming", "--xrim", xrim, stc("t2_box25")])
+    out = [(None, j) for j in jobs]
+    # the standalone programs: generated from the spec's directory (the kernel name is the path minus ".stc")
+    import conftest
+    for name, opts in conftest.EMITTED_PROGRAMS.values():
+        out.append((STC, list(opts) + [name + ".stc"]))
+    _, _, src, opts = wave_cases.CHECK_PROGRAM
+    out.append((os.path.dirname(src), list(opts) + [os.path.basename(src)]))
+    # the six configurations of the tuner smoke run (same space, seed and order as build())
+    from drstencil_amd.tuner import tuning as t
+    t.order, t.ndim, t.elem_bytes = 1, 3, 4
+    paras = t.enumerate_space((1, 2))
+    random.seed(3)
+    random.shuffle(paras)
+    out += [(None, ["--3d", "--dtype", "fp32"] + t.cfgToCommandLine(v).split() + [stc("t3_star")]) for v in paras[:6]]
+    return out
+
+
+def space_sample(per=104, seed=11):
+    """`per` configurations of each of (r3, r4) x (fp32, fp64) on t3_star, steps 1-3, every emission (the space's own filter
+    leaves few for the generator to reject; those pin its error paths)."""
+    from drstencil_amd.tuner import tuning as t
+    out = []
+    for r4 in (False, True):
+        for dtype, eb in (("fp32", 4), ("fp64", 8)):
+            t.order, t.ndim, t.elem_bytes = 1, 3, eb
+            space = t.enumerate_space((1, 2, 3), emits=("taps", "pin", "rows", "rowspk"), round4=r4)
+            rnd = random.Random("%d/%s/%d" % (seed, dtype, r4))
+            for v in rnd.sample(space, per):
+                out.append((None, ["--3d", "--dtype", dtype] + t.cfgToCommandLine(v).split() + [stc("t3_star")]))
+    return out
+
+
+# option values that select an emitter branch: (words on the command line, the bases they are tried on)
+D3 = ["--3d", "--dtype", "fp32", "--step", "2", "--sn", "16", "--prefetch"]
+D3F64 = ["--3d", "--dtype", "fp64", "--sn", "8"]
+PIPE = ["--3d", "--dtype", "fp64", "--step", "3", "--temporal", "force", "--prefetch", "--bx", "34", "--by", "8", "--block-merge-y", "2", "--sn", "16"]
+ROWS = ["--3d", "--dtype", "fp32", "--step", "2", "--sn", "16", "--prefetch", "--order", "rows"]
+TILE = ["--dtype", "fp32"]
+STREAM = ["--dtype", "fp64", "--streaming", "--prefetch"]
+BASES = {"d3": (D3, "smoke3"), "d3f64": (D3F64, "t3_star"), "pipe": (PIPE, "t3_star"), "rows": (ROWS, "smoke3"), "tile": (TILE, "t2_box9"),
+         "stream": (STREAM, "t2_star"), "cross": (["--3d", "--dtype", "fp32", "--dist", "2"], "t3_cross"),
+         "odd": (["--3d", "--dtype", "fp32", "--step", "2"], "t3_star_odd")}     # N = 263: element-wide accesses
+ALL = tuple(BASES)
+KNOBS = [(["--xcd-remap", str(n)], ALL) for n in range(6)] + [
+    (["--xcd-remap", "3", "--zgroup", "2"], ("d3",)), (["--xcd-remap", "5", "--xcd-chunk", "3"], ("d3", "tile")),
+] + [(["--schedule", s, "--lazy-rims", lz], ("d3", "d3f64", "stream", "cross")) for s in ("window", "reuse") for lz in ("0", "1")] + [
+    (["--schedule", "reuse", "--dist", "1", "--merge-forward", mf], ("d3", "cross")) for mf in ("0", "100")] + [
+    (["--stage", "dma"], ("d3", "d3f64", "stream", "cross", "rows")), (["--stage", "dma", "--loader-waves", "2"], ("d3", "d3f64", "stream")),
+    (["--stage", "dma", "--loader-waves", "1", "--prefetch-depth", "1"], ("d3",)), (["--stage", "dma", "--schedule", "window"], ("d3", "cross")),
+    (["--stage", "dma", "--xrim", "lds"], ("d3",)), (["--stage", "dma", "--store-mask", "buffer", "--defer-stores", "1"], ("d3",)),
+    (["--skew", "1"], ("pipe", "d3")), (["--skew", "2"], ("pipe",)), (["--skew", "0"], ("pipe",)),
+    (["--skew", "2", "--order", "rows"], ("pipe",)), (["--skew", "1", "--order", "rows", "--pack", "1", "--dtype", "fp32"], ("pipe",)),
+    (["--temporal", "1"], ("d3", "stream")), (["--temporal", "force", "--exact-y", "1"], ("d3",)),
+    (["--defer-stores", "1"], ("d3", "d3f64", "stream", "cross")), (["--drain", "1"], ("d3", "pipe")), (["--drain", "2"], ("d3", "pipe")),
+    (["--uniform-loads", "1"], ("d3", "stream", "pipe")), (["--uniform-loads", "2"], ("d3", "stream", "pipe")),
+    (["--uniform-loads", "2", "--store-mask", "buffer"], ("d3", "d3f64", "rows")), (["--store-mask", "buffer"], ALL),
+    (["--store-mask", "buffer", "--clamp-loads", "0"], ("d3", "tile")), (["--coef", "sgpr"], ("d3", "rows", "tile", "d3f64")),
+    (["--coef", "vgpr"], ("d3",)), (["--cyclic-merge-x", "4"], ("d3", "tile", "stream", "cross")), (["--cyclic-merge-x", "4", "--xrim", "lds"], ("d3",)),
+    (["--cyclic-merge-y", "2"], ("d3", "tile", "rows")), (["--zigzag", "1"], ("d3", "stream", "tile")),
+    (["--xedge-select", "1"], ("d3", "tile", "cross")), (["--halo-spread", "1"], ("d3", "tile", "d3f64")), (["--xrim", "lds"], ALL),
+] + [(["--nt-load", n], ("d3", "tile")) for n in "123"] + [(["--nt-store", n], ("d3", "tile")) for n in ("0", "1", "16")] + [
+    (["--nt-store", "16", "--store-mask", "buffer", "--nt-load", "1"], ("d3",)), (["--waves-per-eu", "2"], ("d3", "tile")),
+    (["--rot-mod", "8"], ("d3", "rows")), (["--rot-mod", "6"], ("rows",)), (["--stream-unroll", "8"], ("d3", "rows")),
+    (["--order", "rows", "--pack", "1", "--block-merge-x", "2"], ("d3", "tile")), (["--order", "rows", "--pack", "1", "--block-merge-x", "4"], ("d3", "tile")),
+    (["--order", "rows", "--pack", "0"], ("d3", "tile", "stream", "d3f64")), (["--pack", "1", "--xrim", "lds"], ("rows",)),
+    (["--row-fence", "-1"], ("rows",)), (["--row-fence", "7"], ("rows",)), (["--pin", "1"], ("d3", "pipe")), (["--pin", "0"], ("rows", "pipe")),
+] + [(["--debug-skip", str(b)], ("d3", "tile", "rows")) for b in (1, 2, 4, 8, 15)] + [
+    (["--debug-drop-barrier", "1"], ("pipe",)), (["--debug-drop-barrier", "2"], ("d3", "cross")),
+    (["--clamp-loads", "0"], ("d3", "tile", "stream", "pipe")), (["--exact-x", "0"], ("d3", "tile")), (["--exact-y", "0"], ("d3", "tile")),
+    (["--exact-y", "1"], ("pipe",)), (["--prefetch-depth", "2"], ("d3", "pipe", "rows")), (["--prefetch-depth", "4"], ("d3",)),
+    (["--prefetch-auto", "0"], (["--3d", "--dtype", "fp32", "--step", "2"],)), (["--lds-pad", "3"], ("d3", "tile")), (["--out-skew", "8"], ("d3",)),
+    (["--cc-opt", "-fno-slp-vectorize"], ("d3",)), (["--ref-defaults"], ("d3", "tile", "cross")), (["--pair-launch", "1"], ("d3", "stream")),
+    (["--time-order", "2"], ("d3f64", "tile", "cross")), (["--boundary", "periodic"], ("d3f64", "tile", "stream")),
+    (["--step", "3"], ("d3f64", "tile")), (["--tuned-defaults", "0"], ("d3f64",)),
+]
+
+
+def knob_lists():
+    out = []
+    for words, bases in KNOBS:
+        for b in bases:
+            opts, name = BASES[b] if isinstance(b, str) else (b, "t3_star")
+            out.append((None, list(opts) + list(words) + [stc(name)]))
+    return out
+
+
+def host_lists():
+    """The emitted main(): N-GPU hosts, the pair launch, --check with periodic boundaries and second-order time stepping."""
+    wave3 = ["--3d", "--dtype", "fp32", "--time-order", "2", "--check"]
+    return [(None, l) for l in [
+        ["--3d", "--dtype", "fp32", "--step", "2", "--sn", "16", "--gpus", "2", "--check", stc("t3_star")],
+        ["--3d", "--dtype", "fp64", "--gpus", "8", stc("t3_star")],
+        ["--dtype", "fp32", "--streaming", "--step", "2", "--sn", "16", "--gpus", "2", "--check", stc("t2_star")],
+        ["--3d", "--dtype", "fp32", "--sn", "8", "--pair-launch", "1", stc("t3_star")],
+        # periodic: rows of a multiple of 16 bytes (the wrap kernel copies vectors) and not
+        ["--3d", "--dtype", "fp32", "--boundary", "periodic", "--check", stc("smoke3")],
+        ["--3d", "--dtype", "fp32", "--boundary", "periodic", "--check", stc("t3_star")],
+        ["--3d", "--dtype", "fp64", "--boundary", "periodic", "--check", stc("t3_star_odd")],
+        ["--dtype", "fp32", "--boundary", "periodic", "--check", stc("t2_box9")],
+        ["--dtype", "fp32", "--boundary", "periodic", "--check", stc("t2_star")],
+        ["--dtype", "fp64", "--boundary", "periodic", "--check", stc("t2_odd")],
+        wave3 + [stc("t3_wave")], wave3 + ["--store-mask", "buffer", stc("t3_wave")],
+        wave3 + ["--prefetch", "--prefetch-depth", "1", stc("t3_wave")], wave3 + ["--prefetch", "--prefetch-depth", "2", stc("t3_wave")],
+        wave3 + ["--prefetch", "--prefetch-depth", "2", "--store-mask", "buffer", stc("t3_wave")],
+        ["--dtype", "fp64", "--time-order", "2", "--check", stc("t2_wave")],
+        # rejected before the emitter is asked
+        ["--3d", "--boundary", "periodic", "--gpus", "2", stc("t3_star")], ["--3d", "--time-order", "2", "--pair-launch", "1", stc("t3_wave")],
+        ["--3d", "--gpus", "65", stc("t3_star")], ["--3d", "--bogus", stc("t3_star")], ["--3d", "--step", stc("t3_star")],
+        ["--3d", stc("no_such_spec")], ["--help"],
+    ]]
+
+
+def corpus():
+    return build_lists() + space_sample() + host_lists() + knob_lists()
+
+
+def coverage(lists):
+    """Lists of the corpus per option value named in KNOBS (first word pair of each entry)."""
+    seen = {}
+    for words, _ in KNOBS:
+        for i in range(0, len(words) - 1, 2):
+            seen.setdefault((words[i], words[i + 1]), 0)
+    for _, l in lists:
+        for i in range(len(l) - 1):
+            if (l[i], l[i + 1]) in seen:
+                seen[(l[i], l[i + 1])] += 1
+    return seen
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
+    ap.add_argument("outdir")
+    ap.add_argument("--lib", default=os.path.join(ROOT, "drstencil_amd", "libdrstencil_amd.so"))
+    ap.add_argument("--cli", default=None, help="drstencil binary of the same build (default: bin/drstencil two levels above --lib)")
+    ap.add_argument("--coverage", action="store_true")
+    a = ap.parse_args()
+    cli = a.cli or os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(a.lib))), "bin", "drstencil")
+    L = ctypes.CDLL(os.path.abspath(a.lib))
+    L.drs_generate.argtypes = [ctypes.c_int, ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_void_p)]
+    L.drs_free.argtypes = [ctypes.c_void_p]
+
+    def take(p):
+        s = ctypes.string_at(p.value) if p.value else None
+        if p.value:
+            L.drs_free(p.value)
+        return s
+
+    lists = corpus()
+    os.makedirs(a.outdir, exist_ok=True)
+    home = os.getcwd()
+    emitted = rejected = 0
+    with open(os.path.join(a.outdir, "MANIFEST"), "w") as man:
+        for n, (cwd, args) in enumerate(lists):
+            os.chdir(cwd or home)
+            arr = (ctypes.c_char_p * len(args))(*[os.fsencode(x) for x in args])
+            src, msg = ctypes.c_void_p(), ctypes.c_void_p()
+            rc = L.drs_generate(len(args), arr, ctypes.byref(src), ctypes.byref(msg))
+            source, messages = take(src), take(msg) or b""
+            text = b"args: " + " ".join(args).encode() + b"\nexit code: %d\nmessages:\n" % rc + messages
+            if source is None:
+                # why: the command's stderr (nothing is written: a rejected list emits no file)
+                r = subprocess.run([cli] + args, capture_output=True, cwd=cwd or home)
+                text += b"stderr (exit code %d):\n" % r.returncode + r.stderr
+                rejected += 1
+            else:
+                text += b"source:\n" + source
+                emitted += 1
+            os.chdir(home)
+            with open(os.path.join(a.outdir, "%04d.txt" % n), "wb") as f:
+                f.write(text)
+            man.write("%s  %04d  %s\n" % (hashlib.sha256(text).hexdigest(), n, " ".join(args)))
+    digest = hashlib.sha256(open(os.path.join(a.outdir, "MANIFEST"), "rb").read()).hexdigest()
+    print("%d configurations: %d emitted, %d rejected; MANIFEST sha256 %s" % (len(lists), emitted, rejected, digest))
+    if a.coverage:
+        for (k, v), c in sorted(coverage(lists).items()):
+            print("%4d  %s %s" % (c, k, v))
+
+
+if __name__ == "__main__":
+    main()
