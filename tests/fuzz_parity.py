@@ -2,6 +2,8 @@
 """Randomised parity sweep on the GPU: random configurations from the tuner's space (all steps, temporal
 or fused, odd lane counts, both dtypes) on small ragged grids, each compared with the CPU oracle --
 bit for bit for single-pass kernels, within the dtype's bar for temporal pipelines.
+--mode periodic | order2 | order2_periodic (or FUZZ_MODE) draws the same space with --boundary periodic and / or --time-order 2 and
+checks against the oracle with the host wrap in front of every launch / followed by the subtraction of the old output.
 Builds everything before HIP is initialised."""
 import os, random, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))   # tests/ may use the oracle as the checker
@@ -81,52 +83,193 @@ def round4_knobs(rnd, cl):
     return cl
 
 
-def make_jobs(n, seed):
-    """n random configurations (tuner space x test stencils x dtypes): (ndim, stc, dtype, drstencil args, step)."""
-    random.seed(seed)
+MODES = ("fixed", "periodic", "order2", "order2_periodic")
+# the new problem modes draw over the small specs of the periodic and order-2 suites: (ndim, spec, order)
+MODE_STCS = [(3, "t3_star", 1), (3, "t3_star_odd", 1), (3, "t3_cross", 1), (3, "t3_odd", 1), (3, "t3_wave", 1),
+             (2, "t2_star", 1), (2, "t2_box25", 2), (2, "t2_odd", 1), (2, "t2_wave", 1)]
+MODE_OPTS = {"fixed": [], "periodic": ["--boundary", "periodic"], "order2": ["--time-order", "2"],
+             "order2_periodic": ["--time-order", "2", "--boundary", "periodic"]}
+MODE = os.environ.get("FUZZ_MODE", "fixed")             # the manual sweeps' mode (fuzz_parity.py / fuzz_shapes.py; --mode on the command line wins)
+
+
+def job_mode(args):
+    """The problem mode a job's argument list names."""
+    per = "--boundary" in args and args[args.index("--boundary") + 1] == "periodic"
+    o2 = "--time-order" in args and args[args.index("--time-order") + 1] == "2"
+    return "order2_periodic" if per and o2 else "order2" if o2 else "periodic" if per else "fixed"
+
+
+def mode_from_argv(argv):
+    """--mode <m> taken out of argv (default: FUZZ_MODE, else fixed)."""
+    mode = MODE
+    if "--mode" in argv:
+        i = argv.index("--mode")
+        mode = argv[i + 1]
+        del argv[i:i + 2]
+    if mode not in MODES:
+        sys.exit("mode must be one of " + ", ".join(MODES))
+    return mode
+
+
+def make_jobs(n, seed, mode="fixed"):
+    """n random configurations (tuner space x test stencils x dtypes): (ndim, stc, dtype, drstencil args, step).  mode "fixed" is the
+    sweep as it always was (the module-level generator seeded with `seed`: same draws, same jobs, same kernel cache keys).  The other
+    modes draw from a generator of their own over MODE_STCS, n spread evenly over the spec x dtype pairs, append the mode's options and
+    skip draws that the tuner's spill model predicts to be refused for scratch;
+    the order-2 modes keep to what the generator accepts (step 1, no on-chip stages)."""
+    assert mode in MODES, mode
+    if mode == "fixed":
+        random.seed(seed)
+        rnd, stcs = random, STCS
+    else:
+        rnd, stcs = random.Random("%s/%d" % (mode, seed)), MODE_STCS
+    order2 = mode.startswith("order2")
     jobs = []
-    for ndim, name, order in STCS:
+    pair = 0
+    for ndim, name, order in stcs:
         stc = os.path.join(ROOT, "tests", "stc", name + ".stc")
         for dtype in ("fp32", "fp64"):
             t.order, t.ndim, t.elem_bytes = order, ndim, 4 if dtype == "fp32" else 8
             # FUZZ_STEPS="3,4" FUZZ_SPACE_R4=1: the deep pipelines of round 4 (4 on-chip stages; 11-row workgroups, 36 / 68-lane rows, sn 128 / 256)
             steps = tuple(int(x) for x in os.environ.get("FUZZ_STEPS", "1,2,3").split(","))
+            if order2:
+                steps = (1,)
             space = t.enumerate_space(steps if order == 1 else tuple(x for x in steps if x <= 2) or (2,), round4=bool(os.environ.get("FUZZ_SPACE_R4")))
-            for v in random.sample(space, min(len(space), max(1, n // (2 * len(STCS))))):
+            if mode == "fixed":
+                count = max(1, n // (2 * len(stcs)))
+            else:
+                count = n // (2 * len(stcs)) + (pair < n % (2 * len(stcs)))
+                pair += 1
+            # the new modes oversample and drop what the tuner's spill model predicts the runtime would refuse (tuning.registerFilter, as
+            # tests/fuzz_shapes.py does), so that the compiled sample is mostly checked; the fixed sweep compiles every draw, as it always did
+            taken = 0
+            for v in rnd.sample(space, min(len(space), count if mode == "fixed" else 8 * count)):
+                if taken == count:
+                    break
                 cl = t.cfgToCommandLine(v).split()
                 if "cross" in name:
                     i = cl.index("--dist"); cl[i + 1] = str(2 * v[0])
-                if ndim == 2 and random.random() < 0.5:
+                if ndim == 2 and rnd.random() < 0.5:
                     cl.append("--streaming")
                 if "--prefetch-depth" in cl:
-                    cl[cl.index("--prefetch-depth") + 1] = str(random.choice([1, 2, 3, 4]))
+                    cl[cl.index("--prefetch-depth") + 1] = str(rnd.choice([1, 2, 3, 4]))
                 # round-2 knobs: the reuse schedule's --merge-forward on both sides of the retained planes' tap counts, and the
                 # memory path (unconditional / window loads, buffer-masked stores, drains)
-                if "--schedule" not in cl and random.random() < 0.6:
-                    cl[cl.index("--merge-forward") + 1] = str(random.choice([0, 2, 3, 100]))
-                if random.random() < 0.3:
-                    cl += ["--uniform-loads", str(random.choice([1, 2]))]
-                if random.random() < 0.3:
+                if "--schedule" not in cl and rnd.random() < 0.6:
+                    cl[cl.index("--merge-forward") + 1] = str(rnd.choice([0, 2, 3, 100]))
+                if rnd.random() < 0.3:
+                    cl += ["--uniform-loads", str(rnd.choice([1, 2]))]
+                if rnd.random() < 0.3:
                     cl += ["--store-mask", "buffer"]
-                if random.random() < 0.2:
-                    cl += ["--drain", str(random.choice([1, 2]))]
-                if random.random() < 0.3 and "--temporal" not in cl and "--cyclic-merge-y" not in cl and (ndim == 3 or "--streaming" in cl):
+                if rnd.random() < 0.2:
+                    cl += ["--drain", str(rnd.choice([1, 2]))]
+                if rnd.random() < 0.3 and "--temporal" not in cl and "--cyclic-merge-y" not in cl and (ndim == 3 or "--streaming" in cl):
                     cl += ["--stage", "dma"]
-                if random.random() < 0.3:
+                if rnd.random() < 0.3:
                     cl += ["--defer-stores", "1"]
                 if ROUND3:
-                    round3_knobs(random, cl)
+                    round3_knobs(rnd, cl)
                     if os.environ.get("FUZZ_ROUND4", "1") != "0":
-                        round4_knobs(random, cl)
+                        round4_knobs(rnd, cl)
                         if "--skew" in cl and ndim == 2 and "--streaming" not in cl:
                             del cl[cl.index("--skew"):cl.index("--skew") + 2]          # one-shot 2D tiles have no stream to skew
-                args = (["--3d"] if ndim == 3 else []) + ["--dtype", dtype] + cl + [stc]
+                args = (["--3d"] if ndim == 3 else []) + ["--dtype", dtype] + cl + MODE_OPTS[mode] + [stc]
+                if mode != "fixed" and not t.registerFilter(args):
+                    continue
+                taken += 1
                 jobs.append((ndim, stc, dtype, args, v[0]))
     return jobs
 
 
+def signed_random(shape, dtype, seed):
+    """Uniform in [-1, 1): both signs, so that sums and the order-2 subtraction cancel."""
+    return (np.random.default_rng(seed).random(shape) * 2.0 - 1.0).astype(dtype)
+
+
+def mode_inputs(spec, dtype, temporal):
+    """(A0, B0) of a run in one of the new modes: random A AND random B in [-1, 1) -- with B = 0 the first order-2 launch cannot tell
+    -out_old from nothing, and a periodic launch must not read what B's ring holds.  On-chip temporal pipelines (periodic mode only) are
+    held to a RELATIVE bar, which means nothing where a sum cancels to nearly zero (one cell in a million is six digits down), so
+    they keep non-negative data, [0, 1), like every other temporal case of the project."""
+    npdt = np.float32 if dtype == "fp32" else np.float64
+    if temporal:
+        return np.random.default_rng(11).random(spec.shape).astype(npdt), np.random.default_rng(12).random(spec.shape).astype(npdt)
+    return signed_random(spec.shape, npdt, 11), signed_random(spec.shape, npdt, 12)
+
+
+def mode_reference(spec, A, B, launches, mode):
+    """The host reference of `launches` launches of the ping-pong loop in `mode`, in place: the oracle's contracted sweep (fixed),
+    with the host wrap in front of every launch (periodic_cases.oracle_periodic_run), or followed by one subtraction of the old output
+    (wave_cases.host_run, with the wrap where the mode is periodic too)."""
+    import periodic_cases, wave_cases
+    if mode.startswith("order2"):
+        return wave_cases.host_run(spec, A, B, launches, periodic=mode == "order2_periodic")
+    if mode == "periodic":
+        return periodic_cases.oracle_periodic_run(spec, A, B, launches)
+    for i in range(launches):
+        src, dst = (A, B) if i % 2 == 0 else (B, A)
+        oracle.sweep(spec, src, dst, contract=1)
+    return launches
+
+
+def ring_mask(shape, h):
+    ring = np.ones(shape, bool)
+    ring[tuple(slice(h, s - h) for s in shape)] = False
+    return ring
+
+
+def rel_error(got, ref):
+    got, ref = np.asarray(got, np.float64), np.asarray(ref, np.float64)
+    return float(np.max(np.abs(got - ref) / np.maximum(np.abs(ref), 1e-30)))
+
+
+def compare_mode_run(spec, mode, dtype, A0, B0, A, B, Ar, Br, launches, temporal):
+    """(ok, rel): the arrays a run left against the reference's.  Single-pass kernels (and every gold kernel): both arrays bit for
+    bit, which covers the rings -- unchanged under a fixed boundary, the host wrap of the interior under a periodic one.  Temporal
+    periodic pipelines: within 1e-6 (fp32) / 1e-12 (fp64) everywhere, and the ring rule: B, wrapped by the last launch and not
+    written since, is its own host wrap bit for bit; A's ring is exact after two launches (filled from A0's interior) and the wrap of
+    values that are themselves within the bar after more."""
+    h = spec.halo
+    ring = ring_mask(A0.shape, h)
+    if mode in ("fixed", "order2") and not (np.array_equal(A[ring], A0[ring]) and np.array_equal(B[ring], B0[ring])):
+        return False, 0.0
+    if not temporal:
+        return bool(np.array_equal(A, Ar) and np.array_equal(B, Br)), 0.0
+    import periodic_cases
+    rel = max(rel_error(A, Ar), rel_error(B, Br))
+    ring_ok = np.array_equal(B, periodic_cases.host_wrap(B.copy(), h)) and (launches != 2 or np.array_equal(A[ring], Ar[ring]))
+    return bool(rel <= (1e-6 if dtype == "fp32" else 1e-12) and ring_ok), rel
+
+
+def check_mode(job, k, torch, mode):
+    """check() for the periodic / order-2 modes: Kernel.run for the spec's iterations from random A and random B against
+    mode_reference, then the gold kernel from the same inputs against the same reference (always bit for bit)."""
+    ndim, stc, dtype, args, step = job
+    temporal = k.info.get("stages", 1) > 1
+    assert not (temporal and mode != "periodic"), "an order-2 kernel with on-chip stages"
+    assert k.periodic == mode.endswith("periodic") and k.time_order == (2 if mode.startswith("order2") else 1)
+    spec = oracle.Spec(stc, ndim, step)
+    A0, B0 = mode_inputs(spec, dtype, temporal)
+    Ar, Br = A0.copy(), B0.copy()
+    launches = mode_reference(spec, Ar, Br, spec.launches, mode)
+    status, worst = "ok", 0.0
+    for gold in (False, True):
+        dA, dB = torch.from_numpy(A0).cuda(), torch.from_numpy(B0).cuda()
+        n = k.run(dA.data_ptr(), dB.data_ptr(), gold=gold)
+        torch.cuda.synchronize()
+        ok, rel = compare_mode_run(spec, mode, dtype, A0, B0, dA.cpu().numpy(), dB.cpu().numpy(), Ar, Br, launches, temporal and not gold)
+        worst = max(worst, rel)
+        if n != launches or not ok:
+            status = "bad"
+    return status, temporal, worst
+
+
 def check(job, k, torch):
-    """One configuration on the GPU against the oracle: ("ok" | "drift" | "bad", temporal, max relative error)."""
+    """One configuration on the GPU against the oracle: ("ok" | "drift" | "bad", temporal, max relative error).  Jobs of the
+    periodic / order-2 modes (the mode is read off the job's arguments) go through check_mode."""
+    mode = job_mode(job[3])
+    if mode != "fixed":
+        return check_mode(job, k, torch, mode)
     ndim, stc, dtype, args, step = job
     temporal = k.info.get("stages", 1) > 1
     spec = oracle.Spec(stc, ndim, step)
@@ -153,8 +296,9 @@ def check(job, k, torch):
 
 
 def main():
+    mode = mode_from_argv(sys.argv)                   # fuzz_parity.py [--mode periodic | order2 | order2_periodic] <n> <seed>
     n = int(sys.argv[1]) if len(sys.argv) > 1 else 120
-    jobs = make_jobs(n, int(sys.argv[2]) if len(sys.argv) > 2 else 1)
+    jobs = make_jobs(n, int(sys.argv[2]) if len(sys.argv) > 2 else 1, mode)
     t0 = time.time()
     with ProcessPoolExecutor(max_workers=int(os.environ.get("FUZZ_JOBS", "16"))) as ex:
         errs = list(ex.map(build, jobs))

@@ -5,8 +5,11 @@ orders 1-3, on small ragged grids, each with a few random configurations from th
 and some illegal --dist) and compared with the CPU oracle like tests/fuzz_parity.py: bit for bit for single-pass kernels,
 within the dtype's bar for temporal pipelines.  The hand-written test stencils are stars, boxes and crosses; this sweep is
 for everything else the .stc format can say.
-usage: fuzz_shapes.py <shapes> <configurations per shape and dtype> <seed>.  FUZZ_BUILD_ONLY=1 fills the kernel cache on a
-box without a GPU (the .stc files are regenerated from the seed on either side)."""
+usage: fuzz_shapes.py [--mode periodic | order2 | order2_periodic] <shapes> <configurations per shape and dtype> <seed>.
+FUZZ_BUILD_ONLY=1 fills the kernel cache on a box without a GPU (the .stc files are regenerated from the seed on either side).
+--mode (or FUZZ_MODE) adds --boundary periodic and / or --time-order 2 to every configuration (fuzz_parity.check then compares with
+the mode's host reference): periodic configurations whose grid is smaller than 3 Halo of the drawn step in some dimension are skipped
+(the generator would reject them: a legal refusal, not a finding), order 2 keeps to step 1 without on-chip stages."""
 import itertools, os, random, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))   # tests/ may use the oracle as the checker
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
@@ -18,6 +21,7 @@ import fuzz_parity as fp
 
 BIG = bool(os.environ.get("FUZZ_SHAPES_BIG"))
 dropped = [0]         # configurations the tuner's spill model kept from the compiler
+skipped_small = [0]   # periodic configurations on grids smaller than 3 Halo of their step
 MAX_TAPS = int(os.environ.get("FUZZ_MAX_TAPS", "420"))        # fused point count above which a step is not tried (compile time)
 
 
@@ -60,7 +64,8 @@ def legal_dists(pts, step):
     return [d for d in range(1, span + 1) if any((f[0] - d,) + f[1:] in fused for f in fused)]
 
 
-def make_jobs(nshapes, per, seed):
+def make_jobs(nshapes, per, seed, mode="fixed"):
+    assert mode in fp.MODES and not (BIG and mode != "fixed"), mode      # check_gold knows the fixed boundary only
     rnd = random.Random(seed)
     out = os.path.join(ROOT, "gpurun_out", "fuzz_shapes"); os.makedirs(out, exist_ok=True)
     jobs = []
@@ -78,6 +83,8 @@ def make_jobs(nshapes, per, seed):
         write_stc(stc, ndim, dims, rnd.randint(1, 7), pts)     # iterations: 2 * ceil(iterations / (2 * step)) launches (codegen.hpp:581-584)
         distinct = len(set(p[:-1] for p in pts))
         steps = tuple(st for st in (1, 2, 3) if min((2 * h * st + 1) ** ndim, distinct ** st) <= MAX_TAPS)
+        if mode.startswith("order2"):
+            steps = (1,)                         # what the generator accepts with --time-order 2 (no --temporal at step 1 either)
         dists = {}
         for dtype in ("fp32", "fp64"):
             t.order, t.ndim, t.elem_bytes = h, ndim, 4 if dtype == "fp32" else 8
@@ -116,7 +123,10 @@ def make_jobs(nshapes, per, seed):
                     fp.round4_knobs(rnd, cl)
                     if "--skew" in cl and ndim == 2 and "--streaming" not in cl:
                         del cl[cl.index("--skew"):cl.index("--skew") + 2]
-                args = (["--3d"] if ndim == 3 else []) + ["--dtype", dtype] + cl + [stc]
+                if mode.endswith("periodic") and min(dims[3 - ndim:]) < 3 * h * v[0]:
+                    skipped_small[0] += 1        # --boundary periodic needs every dimension >= 3 Halo (Halo = step * order)
+                    continue
+                args = (["--3d"] if ndim == 3 else []) + ["--dtype", dtype] + cl + fp.MODE_OPTS[mode] + [stc]
                 if not t.registerFilter(args):   # the tuner's spill model: do not compile what would be refused for scratch
                     dropped[0] += 1
                     continue
@@ -153,9 +163,12 @@ def check_gold(job, k, torch):
 
 
 def main():
+    mode = fp.mode_from_argv(sys.argv)
     nshapes = int(sys.argv[1]) if len(sys.argv) > 1 else 40
     per = int(sys.argv[2]) if len(sys.argv) > 2 else 6
-    jobs = make_jobs(nshapes, per, int(sys.argv[3]) if len(sys.argv) > 3 else 1)
+    jobs = make_jobs(nshapes, per, int(sys.argv[3]) if len(sys.argv) > 3 else 1, mode)
+    if skipped_small[0]:
+        print("%d periodic configurations skipped: grid smaller than 3 Halo of the drawn step" % skipped_small[0])
     t0 = time.time()
     with ProcessPoolExecutor(max_workers=int(os.environ.get("FUZZ_JOBS", "16"))) as ex:
         errs = list(ex.map(fp.build, jobs, chunksize=4))

@@ -17,7 +17,11 @@ def stc(name):
     return os.path.join(STC, name + ".stc")
 
 
-# (id, ndim, stc, options): every step-1 schedule the generator can emit
+# (id, ndim, stc, options): one seeded case per step-1 schedule (scatter, reuse, window; taps and rows order; register and LDS-DMA staging;
+# 2D tiles and streams) with the store-path knobs --store-mask buffer, --defer-stores and --zigzag in 3D.  Not here: strided merges,
+# loader wavefronts, overlapped x rims, window loads and drains, unpacked rows, coefficients in registers, non-temporal accesses, XCD
+# maps, rotation moduli, prefetch depths beyond 1 -- tests/test_mode_fuzz_cpu.py (explicit cases and a sample of the tuner's space) and
+# tests/test_mode_fuzz_gpu.py cover those
 SMALL = [
     ("3d_star_fp32", 3, stc("t3_star"), ["--3d", "--dtype", "fp32", "--sn", "8"]),
     ("3d_star_oddN_fp64_elem", 3, stc("t3_star_odd"), ["--3d", "--dtype", "fp64"]),
