@@ -222,8 +222,22 @@ class Kernel:
 
     @property
     def periodic(self):
-        """True for kernels generated with --boundary periodic: every launch first fills the input's ring from its interior (wrap())."""
+        """True for kernels generated with --boundary periodic (every axis periodic, however spelled)."""
         return self.info.get("boundary") == "periodic"
+
+    @property
+    def boundaries(self):
+        """The boundary mode of every axis, outermost first: a tuple of "fixed" | "periodic" | "reflect" ((z, y, x) in 3D, (y, x) in 2D),
+        from either form of the kernel info ("boundaries" for reflecting and mixed kernels, "boundary" alone for periodic, neither for
+        fixed)."""
+        if "boundaries" in self.info:
+            return tuple(self.info["boundaries"])
+        return (self.info.get("boundary", "fixed"),) * self.info["ndim"]
+
+    @property
+    def fills_ring(self):
+        """True when some axis is not fixed: every launch first fills the input's ring on those axes from its interior (wrap())."""
+        return any(m != "fixed" for m in self.boundaries)
 
     @property
     def time_order(self):
@@ -232,11 +246,13 @@ class Kernel:
         return int(self.info.get("time_order", 1))
 
     def wrap(self, d, stream=0):
-        """--boundary periodic: fill the ring of width Halo of the device array `d` with the periodic images of its interior (period
-        dim - 2 Halo per dimension), asynchronously on `stream`.  Every launch does this to its input first."""
+        """Kernels with a non-fixed axis (--boundary periodic | reflect, --boundary-x / -y / -z): fill the ring of width Halo of the device
+        array `d` on those axes from its interior (periodic images one period, dim - 2 Halo, away; zero-flux mirror images about the face
+        between ring and interior), asynchronously on `stream`.  The ring of a fixed axis is not written.  Every launch does this to its
+        input first."""
         rc = lib().drs_kernel_wrap(self.h, d, stream)
         if rc == -2:
-            raise RuntimeError("wrap(): the kernel was not generated with --boundary periodic")
+            raise RuntimeError("wrap(): the kernel fills no ring (every axis is fixed: generate it with --boundary periodic | reflect or a per-axis --boundary-x / -y / -z)")
         if rc != 0:
             raise RuntimeError("HIP launch error %d" % rc)
 

@@ -34,7 +34,7 @@ struct drs_kernel {
     int (*launch)(const void *, void *, hipStream_t) = nullptr;
     int (*launch_gold)(const void *, void *, hipStream_t) = nullptr;
     int (*launch_pair)(const void *, void *, const void *, void *, hipStream_t) = nullptr;   // only with --pair-launch 1
-    int (*wrap)(void *, hipStream_t) = nullptr;              // only with --boundary periodic
+    int (*wrap)(void *, hipStream_t) = nullptr;              // only with a non-fixed boundary (--boundary periodic / reflect, --boundary-x / -y / -z)
     const char *(*info)(void) = nullptr;
     std::string path;
     std::string resources;   // JSON: register / scratch / LDS use of dr_<name> as reported by the compiler
@@ -398,7 +398,7 @@ int drs_kernel_launch_pair(drs_kernel *k, const void *d_in0, void *d_out0, const
     return k->launch_pair(d_in0, d_out0, d_in1, d_out1, (hipStream_t)stream);
 }
 int drs_kernel_wrap(drs_kernel *k, void *d, void *stream) {
-    if (!k->wrap) return -2;             // the kernel was not generated with --boundary periodic
+    if (!k->wrap) return -2;             // the kernel fills no ring: every axis is fixed
     g_launched = true;
     return k->wrap(d, (hipStream_t)stream);
 }

@@ -1,5 +1,5 @@
 // emit_host.hpp -- the text of an emitted file that is not the tuned kernel: the gold kernel (reference: codegen.hpp:637-660), the
-// wrap kernel of --boundary periodic, the plugin entry points with the info JSON, and the two host programs (the reference's harness,
+// ring-fill (wrap) kernel of the non-fixed boundaries, the plugin entry points with the info JSON, and the two host programs (the reference's harness,
 // codegen.hpp:547-635, and the N-GPU launcher of --gpus N).  Free functions of the const plan and the Schedule: none of them sees
 // the kernel emitter's state.  HipEmitter::source() (emit_hip.hpp) concatenates the pieces.
 #pragma once
@@ -52,60 +52,95 @@ inline std::string gold_kernel(const KernelPlan &p) {
     return g.str();
 }
 
-// ---- periodic boundaries (--boundary periodic) ----------------------------------------------------------------------------------
-// Lanes [0, ghost rows * accesses per row): the ghost rows -- rows (k, j) with k or j in the ring -- each copied whole from the interior
-// row (w(k), w(j)), its ring columns wrapped inside the lane's own vector (one lane writes every element of a destination vector).  Then
-// one lane per side of every interior row: its Halo x ghosts.  Sources are interior elements, destinations ring elements, and every
-// ring element has one writer: no ordering inside the launch.
+// ---- non-fixed boundaries (--boundary periodic | reflect, --boundary-z / -y / -x) ---------------------------------------------------
+// The ring fill.  Each axis maps a ring coordinate to an interior one (periodic: one period away; reflect: mirrored about the face between
+// ring and interior; fixed: the identity, and that axis has no ring to fill).  Lanes [0, ghost rows * accesses per row): the ghost rows --
+// rows (k, j) with k or j in the ring of a non-fixed axis -- each copied whole from row (map_z(k), map_y(j)), its x-ring columns mapped inside
+// the lane's own vector (one lane writes every element of a destination vector; with x fixed they are copied straight).  Then, unless x is
+// fixed, one lane per side of every other row: its Halo x ghosts.  A source's non-fixed coordinates are all interior and every destination
+// has a coordinate in the ring of a non-fixed axis, so no source is a destination; every destination has one writer: no ordering inside
+// the launch.
 inline long wrap_planes(const KernelPlan &p) { return p.ndim == 3 ? p.L : 1; }
-inline long wrap_zhalo(const KernelPlan &p) { return p.ndim == 3 ? p.halo : 0; }
+inline long wrap_zhalo(const KernelPlan &p) { return p.ndim == 3 && p.bmode[0] != FIXED ? p.halo : 0; }
+inline long wrap_yhalo(const KernelPlan &p) { return p.bmode[1] != FIXED ? p.halo : 0; }
 inline int wrap_vl(const KernelPlan &p) { return ((long)p.N * (p.fp32 ? 4 : 8)) % 16 == 0 ? 16 / (p.fp32 ? 4 : 8) : 1; }   // 16-byte vectors when rows stay aligned
-inline long wrap_ghost_rows(const KernelPlan &p) { return 2 * wrap_zhalo(p) * p.M + (wrap_planes(p) - 2 * wrap_zhalo(p)) * 2 * p.halo; }
-inline long wrap_sides(const KernelPlan &p) { return (wrap_planes(p) - 2 * wrap_zhalo(p)) * (p.M - 2 * p.halo) * 2; }
+inline long wrap_ghost_rows(const KernelPlan &p) { return 2 * wrap_zhalo(p) * p.M + (wrap_planes(p) - 2 * wrap_zhalo(p)) * 2 * wrap_yhalo(p); }
+inline long wrap_sides(const KernelPlan &p) { return p.bmode[2] != FIXED ? (wrap_planes(p) - 2 * wrap_zhalo(p)) * (p.M - 2 * wrap_yhalo(p)) * 2 : 0; }
 inline long wrap_grid(const KernelPlan &p) { return (wrap_ghost_rows(p) * (p.N / wrap_vl(p)) + wrap_sides(p) + 255) / 256; }
 inline std::string wrap_kernel(const KernelPlan &p) {
     std::ostringstream w;
     const int vl = wrap_vl(p);
-    w << "// ---- periodic boundaries: wrap_" << p.name << "(a) fills a's ring of width Halo with the periodic images of a's interior (period\n"
-         "// dim - 2 Halo; the ghost at x takes x + P below Halo and x - P from dim - Halo on, each coordinate wrapped on its own).  Every ring\n"
-         "// element is written once, by one lane, from an interior element: one launch, no barrier.  Ghost rows (z-ghost planes, y-ghost rows)\n"
-         "// are whole-row copies in " << (vl > 1 ? "16-byte vectors" : "elements (N * sizeof(real_t) is not a multiple of 16)")
-      << ", then one lane per side of every interior row writes\n// its Halo x ghosts.  64-bit offsets throughout.\n";
+    const int mz = p.bmode[0], my = p.bmode[1], mx = p.bmode[2];
+    const bool any_reflect = mz == REFLECT || my == REFLECT || mx == REFLECT;
+    // a coordinate's map as emitted: the helper of the axis's mode; a fixed y or x coordinate stands for itself (z: a ring of width DRS_WHZ = 0)
+    auto map = [](int mode, const std::string &x, const char *n, const char *h) {
+        return mode == FIXED ? x : std::string(mode == REFLECT ? "drs_mirror(" : "drs_wrap(") + x + ", " + n + ", " + h + ")";
+    };
+    const std::string map_z = map(mz == REFLECT ? REFLECT : PERIODIC, "k", "DRS_WL", "DRS_WHZ"), map_y = map(my, "j", "M", "Halo");
+    const std::string vec_kind = vl > 1 ? "16-byte vectors" : "elements (N * sizeof(real_t) is not a multiple of 16)";
+    if (p.periodic)
+        w << "// ---- periodic boundaries: wrap_" << p.name << "(a) fills a's ring of width Halo with the periodic images of a's interior (period\n"
+             "// dim - 2 Halo; the ghost at x takes x + P below Halo and x - P from dim - Halo on, each coordinate wrapped on its own).  Every ring\n"
+             "// element is written once, by one lane, from an interior element: one launch, no barrier.  Ghost rows (z-ghost planes, y-ghost rows)\n"
+             "// are whole-row copies in " << vec_kind << ", then one lane per side of every interior row writes\n// its Halo x ghosts.  64-bit offsets throughout.\n";
+    else {
+        w << "// ---- boundaries (" << (p.ndim == 3 ? std::string("z ") + boundary_mode_name(mz) + ", " : std::string()) << "y " << boundary_mode_name(my) << ", x "
+          << boundary_mode_name(mx) << "): wrap_" << p.name << "(a) fills a's ring of width Halo on the non-fixed axes from a's interior.  A ring\n"
+             "// coordinate c of a periodic axis takes c + P below Halo and c - P from dim - Halo on (P = dim - 2 Halo); of a reflecting axis 2 Halo - 1 - c\n"
+             "// and 2 (dim - Halo) - 1 - c (the zero-flux mirror about the face between ring and interior); a fixed axis keeps c, and its ring is never\n"
+             "// written.  A cell is filled iff a coordinate of it lies in the ring of a non-fixed axis, once, by one lane, from the cell with every\n"
+             "// coordinate mapped on its own: one launch, no barrier.  Ghost rows (k or j in such a ring) are whole-row copies in " << vec_kind << ";\n"
+             "// " << (mx != FIXED ? "then one lane per side of every other row writes its Halo x ghosts" : "x is fixed: no other row is touched") << ".  64-bit offsets throughout.\n";
+    }
     w << "#define DRS_WL " << wrap_planes(p) << "L          // planes of the grid (1 in 2D)\n";
-    w << "#define DRS_WHZ " << wrap_zhalo(p) << "L         // ghost planes per side (0 in 2D)\n";
+    w << "#define DRS_WHZ " << wrap_zhalo(p) << (p.periodic ? "L         // ghost planes per side (0 in 2D)\n" : "L         // ghost planes per side (0: z is fixed, or 2D)\n");
     w << "#define DRS_WNV " << p.N / vl << "L        // accesses per ghost row\n";
     w << "#define DRS_WROWS " << wrap_ghost_rows(p) << "L    // ghost rows\n";
-    w << "#define DRS_WSIDES " << wrap_sides(p) << "L   // sides of the interior rows\n";
+    w << "#define DRS_WSIDES " << wrap_sides(p) << (p.periodic ? "L   // sides of the interior rows\n" : "L   // sides of the rows that are no ghost rows (0: x is fixed)\n");
     w << "#define DRS_WGRID " << wrap_grid(p) << "\n";
     if (vl > 1) w << "typedef real_t drs_wvec_t __attribute__((ext_vector_type(" << vl << ")));\n";
     w << "__device__ __forceinline__ long drs_wrap(long x, long n, long h) { return x < h ? x + (n - 2 * h) : (x >= n - h ? x - (n - 2 * h) : x); }\n";
+    if (any_reflect) w << "__device__ __forceinline__ long drs_mirror(long x, long n, long h) { return x < h ? 2 * h - 1 - x : (x >= n - h ? 2 * (n - h) - 1 - x : x); }\n";
     w << "extern \"C\" __global__ void __launch_bounds__(256) wrap_" << p.name << " (real_t* __restrict__ a)\n{\n";
     w << "    const long t = (long)blockIdx.x * 256 + threadIdx.x;\n";
     w << "    if (t < DRS_WROWS * DRS_WNV) {\n";
     w << "        const long r = t / DRS_WNV, v = t - r * DRS_WNV;\n";
     w << "        long k, j;\n";
-    w << "        if (r < 2 * DRS_WHZ * M) { const long q = r / M; j = r - q * M; k = q < DRS_WHZ ? q : DRS_WL - 2 * DRS_WHZ + q; }\n";
-    w << "        else { const long e = r - 2 * DRS_WHZ * M, q = e / (2 * Halo), c = e - q * (2 * Halo); k = DRS_WHZ + q; j = c < Halo ? c : M - 2 * Halo + c; }\n";
+    if (my != FIXED) {
+        w << "        if (r < 2 * DRS_WHZ * M) { const long q = r / M; j = r - q * M; k = q < DRS_WHZ ? q : DRS_WL - 2 * DRS_WHZ + q; }\n";
+        w << "        else { const long e = r - 2 * DRS_WHZ * M, q = e / (2 * Halo), c = e - q * (2 * Halo); k = DRS_WHZ + q; j = c < Halo ? c : M - 2 * Halo + c; }\n";
+    } else      // y is fixed: every ghost row lies in a z-ghost plane
+        w << "        { const long q = r / M; j = r - q * M; k = q < DRS_WHZ ? q : DRS_WL - 2 * DRS_WHZ + q; }\n";
     w << "        real_t* d = a + (k * M + j) * N;\n";
-    w << "        const real_t* s = a + (drs_wrap(k, DRS_WL, DRS_WHZ) * M + drs_wrap(j, M, Halo)) * N;\n";
+    w << "        const real_t* s = a + (" << map_z << " * M + " << map_y << ") * N;\n";
     if (vl > 1) {
         w << "        const long x = v * " << vl << ";\n";
-        w << "        drs_wvec_t u;\n";
-        w << "        if (x >= Halo && x + " << vl << " <= N - Halo) u = *(const drs_wvec_t*)(s + x);\n";
-        w << "        else {\n";
-        for (int e = 0; e < vl; e++) w << "            u[" << e << "] = s[drs_wrap(x + " << e << ", N, Halo)];\n";
-        w << "        }\n";
-        w << "        *(drs_wvec_t*)(d + x) = u;\n";
+        if (mx != FIXED) {
+            w << "        drs_wvec_t u;\n";
+            w << "        if (x >= Halo && x + " << vl << " <= N - Halo) u = *(const drs_wvec_t*)(s + x);\n";
+            w << "        else {\n";
+            for (int e = 0; e < vl; e++) w << "            u[" << e << "] = s[" << map(mx, "x + " + std::to_string(e), "N", "Halo") << "];\n";
+            w << "        }\n";
+            w << "        *(drs_wvec_t*)(d + x) = u;\n";
+        } else      // x is fixed: the source row's x-ring columns come along unchanged
+            w << "        *(drs_wvec_t*)(d + x) = *(const drs_wvec_t*)(s + x);\n";
     } else {
-        w << "        d[v] = s[drs_wrap(v, N, Halo)];\n";
+        w << "        d[v] = s[" << map(mx, "v", "N", "Halo") << "];\n";
     }
-    w << "    } else if (t < DRS_WROWS * DRS_WNV + DRS_WSIDES) {\n";
-    w << "        const long q = t - DRS_WROWS * DRS_WNV, r = q >> 1, pl = r / (M - 2 * Halo);\n";
-    w << "        real_t* row = a + ((DRS_WHZ + pl) * M + Halo + (r - pl * (M - 2 * Halo))) * N;\n";
-    w << "        const long x0 = (q & 1) ? N - Halo : 0, from = (q & 1) ? -(N - 2 * Halo) : (N - 2 * Halo);   // right side : left side\n";
-    w << "        real_t g[Halo];\n";
-    w << "#pragma unroll\n        for (int e = 0; e < Halo; e++) g[e] = row[x0 + from + e];\n";
-    w << "#pragma unroll\n        for (int e = 0; e < Halo; e++) row[x0 + e] = g[e];\n";
+    if (mx != FIXED) {
+        const std::string rows = my != FIXED ? "(M - 2 * Halo)" : "M", y0 = my != FIXED ? "Halo + " : "";
+        w << "    } else if (t < DRS_WROWS * DRS_WNV + DRS_WSIDES) {\n";
+        w << "        const long q = t - DRS_WROWS * DRS_WNV, r = q >> 1, pl = r / " << rows << ";\n";
+        w << "        real_t* row = a + ((DRS_WHZ + pl) * M + " << y0 << "(r - pl * " << rows << ")) * N;\n";
+        if (mx == PERIODIC)
+            w << "        const long x0 = (q & 1) ? N - Halo : 0, from = (q & 1) ? -(N - 2 * Halo) : (N - 2 * Halo);   // right side : left side\n";
+        else
+            w << "        const long x0 = (q & 1) ? N - Halo : 0, from = (q & 1) ? -Halo : Halo;   // right side : left side; the Halo interior cells next to the face\n";
+        w << "        real_t g[Halo];\n";
+        w << "#pragma unroll\n        for (int e = 0; e < Halo; e++) g[e] = row[x0 + from + e];\n";
+        if (mx == PERIODIC) w << "#pragma unroll\n        for (int e = 0; e < Halo; e++) row[x0 + e] = g[e];\n";
+        else w << "#pragma unroll\n        for (int e = 0; e < Halo; e++) row[x0 + e] = g[Halo - 1 - e];   // mirrored: reversed\n";
+    }
     w << "    }\n}\n\n";
     return w.str();
 }
@@ -129,6 +164,10 @@ inline std::string info_json(const Schedule &s) {
         const int H = p.halo;
         j.insert(j.size() - 1, p.ndim == 3 ? sfmt(",\\\"boundary\\\":\\\"periodic\\\",\\\"period\\\":[%d,%d,%d]", p.L - 2 * H, p.M - 2 * H, p.N - 2 * H)
                                            : sfmt(",\\\"boundary\\\":\\\"periodic\\\",\\\"period\\\":[%d,%d]", p.M - 2 * H, p.N - 2 * H));
+    } else if (p.fills_ring()) {
+        std::string axes;
+        for (int a = p.ndim == 3 ? 0 : 1; a < 3; a++) axes += sfmt("%s\\\"%s\\\"", axes.empty() ? "" : ",", boundary_mode_name(p.bmode[a]));
+        j.insert(j.size() - 1, sfmt(",\\\"boundary\\\":\\\"%s\\\",\\\"boundaries\\\":[%s]", p.all_axes(REFLECT) ? "reflect" : "mixed", axes.c_str()));
     }
     return j;
 }
@@ -138,13 +177,13 @@ inline std::string plugin_api(const Schedule &s) {
     const KernelPlan &p = s.p; const GenOptions &o = s.o;
     std::ostringstream a;
     a << "// ---- launch entry points: bound by libdrstencil_amd's runtime (dlopen) and used by main() below\n";
-    if (p.periodic) {
-        a << "// --boundary periodic: drs_plugin_wrap fills a's ring from a's interior; both launch entry points call it on `in` first (same stream)\n";
+    if (p.fills_ring()) {
+        a << "// " << joined(boundary_words(p.ndim, p.bmode)) << ": drs_plugin_wrap fills a's ring from a's interior; both launch entry points call it on `in` first (same stream)\n";
         a << "extern \"C\" int drs_plugin_wrap(void* a, hipStream_t stream)\n{\n";
         a << "    hipLaunchKernelGGL(wrap_" << p.name << ", dim3(DRS_WGRID), dim3(256), 0, stream, (real_t*)a);\n";
         a << "    return (int)hipGetLastError();\n}\n";
     }
-    const std::string wrap_in = p.periodic ? "    if (int rc = drs_plugin_wrap((void*)in, stream)) return rc;\n" : "";
+    const std::string wrap_in = p.fills_ring() ? "    if (int rc = drs_plugin_wrap((void*)in, stream)) return rc;\n" : "";
     a << "extern \"C\" int drs_plugin_launch(const void* in, void* out, hipStream_t stream)\n{\n" << wrap_in;
     a << "    hipLaunchKernelGGL(dr_" << p.name << ", dim3(DRS_GRID), dim3(DRS_NTL), 0, stream, (const real_t*)in, (real_t*)out);\n";
     a << "    return (int)hipGetLastError();\n}\n";

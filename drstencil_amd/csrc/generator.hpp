@@ -104,13 +104,24 @@ Options:
 MI355X options:
 
 --dtype <fp32|fp64>     Element type (fp64 by default, as the reference).
---boundary <fixed|periodic>  fixed (default): the ring of width Halo (= step * order) around the interior is input that no launch
-                        writes (the reference's semantics).  periodic: the interior is a periodic domain of period dim - 2 * Halo
-                        in every dimension (so the period depends on --step) and the ring holds its ghost copies: the ghost at x
-                        takes the value at x + P (x < Halo) or x - P (x >= dim - Halo), each coordinate wrapped on its own.  Every
-                        launch (in -> out) first refills in's ring from in's interior -- it OVERWRITES the input array's ring --
-                        then sweeps as with fixed; out's ring is not touched.  Needs every dimension >= 3 * Halo; not with
-                        --gpus N > 1 or --pair-launch 1.
+--boundary <fixed|periodic|reflect>  The boundary treatment of every axis.  fixed (default): the ring of width Halo (= step * order)
+                        around the interior is input that no launch writes (the reference's semantics).  periodic: the interior is
+                        a periodic domain of period dim - 2 * Halo in every dimension (so the period depends on --step) and the ring
+                        holds its ghost copies: the ghost at x takes the value at x + P (x < Halo) or x - P (x >= dim - Halo), each
+                        coordinate wrapped on its own.  reflect: zero-flux (insulated / rigid) walls on the faces between ring and
+                        interior: the ghost at distance d outside a face takes the interior cell at distance d - 1 inside it (x <
+                        Halo takes 2 Halo - 1 - x, x >= dim - Halo takes 2 (dim - Halo) - 1 - x; numpy's pad mode "symmetric").  Every
+                        launch (in -> out) first refills in's ring from in's interior -- it OVERWRITES the input array's ring on
+                        the non-fixed axes -- then sweeps as with fixed; out's ring is not touched.  A non-fixed axis needs a
+                        dimension >= 3 * Halo; not with --gpus N > 1 or --pair-launch 1.  A fused --step n launch applies S^n to
+                        the mirrored extension, which is n mirrored one-step updates only for a stencil that is symmetric along
+                        every reflecting axis (a note says so otherwise).
+--boundary-x <fixed|periodic|reflect>  The boundary treatment of the x axis alone, overriding --boundary there wherever it stands on the
+                        line (a channel: --boundary periodic --boundary-z reflect).  A ring cell is refilled iff one of its
+                        coordinates lies in the ring of a non-fixed axis; its source has every coordinate mapped on its own, fixed
+                        axes unchanged.  Three equal per-axis values are --boundary <value>.
+--boundary-y <fixed|periodic|reflect>  The same for the y axis.
+--boundary-z <fixed|periodic|reflect>  The same for the z axis (only fixed in 2D).
 --time-order <1|2>      1 (default): out = S(in), a first-order update.  2: out = S(in) - out_old on the interior, the leapfrog
                         update of a second-order equation (wave equation: u(t+1) = S(u(t)) - u(t-1), the factor 2 of 2u folded
                         into the centre coefficient).  The ping-pong loop k(A,B); k(B,A) is then leapfrog as it stands: the
@@ -251,7 +262,10 @@ inline constexpr Opt kOptions[] = {
     {"--stream-unroll", &GenOptions::stream_unroll}, {"--prefetch", &GenOptions::prefetch}, {"--merge-forward", &GenOptions::merge_forward},
     {"--check", &GenOptions::check, NAMES | LOCAL}, {"--gold", &GenOptions::gold, NAMES | LOCAL},
     // additive MI355X options
-    {"--dtype", &GenOptions::dtype, "fp32 fp64", NAMES}, {"--boundary", &GenOptions::boundary, "fixed periodic", NAMES},
+    {"--dtype", &GenOptions::dtype, "fp32 fp64", NAMES}, {"--boundary", &GenOptions::boundary, "fixed periodic reflect", NAMES},
+    {"--boundary-x", &GenOptions::boundary_x, "fixed periodic reflect", NAMES, &GenOptions::boundary_x_set},
+    {"--boundary-y", &GenOptions::boundary_y, "fixed periodic reflect", NAMES, &GenOptions::boundary_y_set},
+    {"--boundary-z", &GenOptions::boundary_z, "fixed periodic reflect", NAMES, &GenOptions::boundary_z_set},
     {"--time-order", &GenOptions::time_order, NAMES},
     {"--gpus", &GenOptions::gpus, NAMES | LOCAL}, {"--pair-launch", &GenOptions::pair_launch, NAMES}, {"--temporal", put_temporal, NAMES},
     {"--out-skew", &GenOptions::out_skew, NAMES}, {"--tuned-defaults", &GenOptions::tuned_defaults, NAMES},
@@ -284,7 +298,14 @@ inline bool scan_options(const std::vector<std::string> &args, GenResult &res, s
     GenOptions &o = res.opt = GenOptions();
     banner.clear();
     auto illegal = [&](int code) { res.messages += "Illegal input.\n"; res.exit_code = code; return false; };
-    auto echo = [&](const std::string &w, bool slab) { banner += (banner.empty() ? "" : " ") + w; if (slab) o.slab_args.push_back(w); };
+    // With a per-axis boundary option on the line the four boundary options are echoed once, in canonical spelling (plan.hpp:
+    // boundary_words), where the first of them stands: three equal per-axis values are the same command as --boundary v, and all-fixed
+    // leaves no trace.  Without one, --boundary is echoed where it stands, as it always was.
+    struct Echo { std::string w; bool slab, boundary; };
+    std::vector<Echo> words;
+    long first_boundary = -1;
+    bool per_axis = false;
+    auto echo = [&](const std::string &w, bool slab) { words.push_back({w, slab, false}); };
     for (size_t i = 0, stc = args.size() - 1; i < stc; i++) {
         const std::string &a = args[i];
         const Opt *r = std::find_if(std::begin(kOptions), std::end(kOptions), [&](const Opt &x) { return a == x.name; });
@@ -303,18 +324,30 @@ inline bool scan_options(const std::vector<std::string> &args, GenResult &res, s
         else if (r->s) o.*r->s = v;
         else if (!r->put(o, v)) return illegal(255);
         if (r->mark) o.*r->mark = true;
-        // `--boundary fixed` is the default spelled out: it leaves no trace in the emitted source (banner and slab host alike)
-        if (a == "--boundary" && v == "fixed") continue;
+        if (a.compare(0, 10, "--boundary") == 0) {
+            if (first_boundary < 0) first_boundary = (long)words.size();
+            if (a != "--boundary") per_axis = true;
+            // `--boundary fixed` is the default spelled out: it leaves no trace in the emitted source (banner and slab host alike)
+            else if (v != "fixed") { words.push_back({a, true, true}); words.push_back({v, true, true}); }
+            continue;
+        }
         if (a == "--time-order" && o.time_order == 1) continue;       // likewise
         echo(a, !(r->attr & LOCAL));
         if (!flag) echo(v, !(r->attr & LOCAL));
     }
     for (const Opt &r : kOptions)
-        if (r.pick && !picks(r.pick, o.*r.s)) return illegal(255);
+        if (r.pick && (!r.mark || o.*r.mark || !(o.*r.s).empty()) && !picks(r.pick, o.*r.s)) return illegal(255);
     if (o.step < 1) return illegal(255);
     if (o.time_order != 1 && o.time_order != 2) return illegal(255);
     // an explicit --dist selects the reference's kind of reuse: `Range` source planes resident, the rest carried as partial sums
     if (!o.schedule_set && o.dist != 0) o.schedule = "reuse";
+    if (per_axis) {
+        words.erase(std::remove_if(words.begin(), words.end(), [](const Echo &e) { return e.boundary; }), words.end());
+        const int m[3] = {boundary_mode_of(o.axis_boundary(0)), boundary_mode_of(o.axis_boundary(1)), boundary_mode_of(o.axis_boundary(2))};
+        long at = first_boundary;
+        for (auto &w : boundary_words(o.is3d ? 3 : 2, m)) words.insert(words.begin() + at++, {w, true, true});
+    }
+    for (auto &e : words) { banner += (banner.empty() ? "" : " ") + e.w; if (e.slab) o.slab_args.push_back(e.w); }
     return true;
 }
 
@@ -364,11 +397,16 @@ inline GenResult generate(const std::vector<std::string> &args /* argv[1..] */) 
     if (!res.plan.error.empty()) { res.messages += "Invalid configuration!\n"; res.exit_code = 255; res.error = res.plan.error; return res; }
     if (!res.plan.note.empty()) res.messages += "drstencil: note: " + res.plan.note + "\n";
     if (o.gpus < 1 || o.gpus > 64) { res.messages += "Illegal input.\n"; res.exit_code = 255; return res; }
-    if (res.plan.periodic && (o.gpus > 1 || o.pair_launch)) {
+    if (res.plan.fills_ring() && (o.gpus > 1 || o.pair_launch)) {
         // periodic z (y in 2D) across ranks would need a rank 0 <-> rank N-1 exchange; the pair kernel exists only for slab views
         res.messages += "Invalid configuration!\n"; res.exit_code = 255;
-        res.error = o.gpus > 1 ? "--boundary periodic cannot be combined with --gpus N > 1 (the slab runtime has no periodic exchange)"
-                                    : "--boundary periodic cannot be combined with --pair-launch 1 (the pair kernel serves the slab runtime, which has no periodic exchange)";
+        if (res.plan.periodic)
+            res.error = o.gpus > 1 ? "--boundary periodic cannot be combined with --gpus N > 1 (the slab runtime has no periodic exchange)"
+                                   : "--boundary periodic cannot be combined with --pair-launch 1 (the pair kernel serves the slab runtime, which has no periodic exchange)";
+        else      // the slab views' rings are ghost planes of their neighbours: no view may refill its own
+            res.error = joined(boundary_words(st.ndim, res.plan.bmode, false)) +
+                        (o.gpus > 1 ? " cannot be combined with --gpus N > 1 (the slab runtime keeps every axis fixed: a slab view has no ring fill)"
+                                    : " cannot be combined with --pair-launch 1 (the pair kernel serves the slab runtime, which keeps every axis fixed)");
         return res;
     }
     if (res.plan.second_order && (o.gpus > 1 || o.pair_launch)) {
@@ -389,6 +427,29 @@ inline GenResult generate(const std::vector<std::string> &args /* argv[1..] */) 
         std::string per = st.ndim == 3 ? std::to_string(st.L - 2 * H) + " x " : "";
         per += std::to_string(st.M - 2 * H) + " x " + std::to_string(st.N - 2 * H);
         res.notes += "drstencil: note: periodic boundaries: period " + per + ", ring of width " + std::to_string(H) + " holds ghost copies\n";
+    } else if (res.plan.fills_ring()) {
+        std::string axes;
+        for (int a = st.ndim == 3 ? 0 : 1; a < 3; a++) axes += std::string(axes.empty() ? "" : ", ") + "zyx"[a] + " " + boundary_mode_name(res.plan.bmode[a]);
+        res.notes += "drstencil: note: boundaries per axis: " + axes + "; the ring of width " + std::to_string(st.halo) +
+                     " on the non-fixed axes holds ghost copies (periodic images / zero-flux mirror images of the interior)\n";
+    }
+    if (o.step > 1) {
+        // a fused launch (and a temporal pipeline) applies S^n to the mirrored extension: n mirrored one-step updates only when the one-step
+        // stencil is its own mirror image along every reflecting axis
+        std::string odd;
+        for (int a = 0; a < 3; a++) {
+            if (res.plan.bmode[a] != REFLECT) continue;
+            bool sym = true;
+            for (auto &e : st.base.v) {
+                Pt m = e.first;
+                (a == 0 ? m.k : a == 1 ? m.j : m.i) = -e.first.at(a);
+                sym = sym && st.base.has(m) && st.base.get(m) == e.second;
+            }
+            if (!sym) odd += std::string(odd.empty() ? "" : ", ") + "zyx"[a];
+        }
+        if (!odd.empty())
+            res.notes += "drstencil: note: the one-step stencil is not symmetric along the reflecting axis " + odd + ": a --step " + std::to_string(o.step) +
+                         " launch applies the fused stencil to the mirrored extension, which differs from " + std::to_string(o.step) + " mirrored one-step updates near those walls\n";
     }
     if (res.plan.second_order)
         res.notes += "drstencil: note: second-order time stepping: a launch computes out = S(in) - out_old on the interior (the output array's interior is input)\n";

@@ -169,11 +169,37 @@ struct GenOptions {
     int row_fence = 0;           // mask of __builtin_amdgcn_sched_barrier between row groups (0: nothing crosses; -1: no fence)
     std::string boundary = "fixed";   // --boundary fixed: the ring of width Halo is frozen input (the reference's Dirichlet boundary);
                                  // periodic: the ring holds ghost copies of the interior, refilled from the input's interior by wrap_<name> at the
-                                 // start of every launch (period dim - 2 Halo per dimension).  It names the problem, not a tuning choice
+                                 // start of every launch (period dim - 2 Halo per dimension); reflect: the ring holds the zero-flux mirror image
+                                 // of the interior about the face between ring and interior.  It names the problem, not a tuning choice
+    std::string boundary_z, boundary_y, boundary_x;   // --boundary-z / -y / -x: one axis's mode, overriding --boundary wherever it stands on the line
+    bool boundary_z_set = false, boundary_y_set = false, boundary_x_set = false;
+    // the mode of axis 0 (z), 1 (y), 2 (x) as resolved from the four options
+    const std::string &axis_boundary(int axis) const {
+        const bool own = axis == 0 ? boundary_z_set : axis == 1 ? boundary_y_set : boundary_x_set;
+        return !own ? boundary : axis == 0 ? boundary_z : axis == 1 ? boundary_y : boundary_x;
+    }
     int time_order = 1;          // --time-order 2: a launch computes out = S(in) - out_old on the interior (the leapfrog update of a second-order
                                  // equation, u(t+1) = S(u(t)) - u(t-1): the ping-pong loop k(A,B); k(B,A) is then leapfrog as it stands).  The old
                                  // output is a third memory stream of the sweep, read once.  It names the problem, not a tuning choice
 };
+
+// ---- boundary modes per axis (0 z, 1 y, 2 x; z counts as fixed in 2D)
+enum BoundaryMode { FIXED = 0, PERIODIC = 1, REFLECT = 2 };
+inline const char *boundary_mode_name(int m) { return m == PERIODIC ? "periodic" : m == REFLECT ? "reflect" : "fixed"; }
+inline int boundary_mode_of(const std::string &v) { return v == "periodic" ? PERIODIC : v == "reflect" ? REFLECT : FIXED; }
+// the boundary options in canonical spelling: nothing (all axes fixed), {"--boundary", v} (all axes v), else one --boundary-<axis> pair
+// per axis in z, y, x order (every axis when `with_fixed`, else only the non-fixed ones)
+inline std::vector<std::string> boundary_words(int ndim, const int m[3], bool with_fixed = true) {
+    const int first = ndim == 3 ? 0 : 1;
+    bool same = true;
+    for (int a = first; a < 3; a++) same = same && m[a] == m[2];
+    if (same) return m[2] == FIXED ? std::vector<std::string>{} : std::vector<std::string>{"--boundary", boundary_mode_name(m[2])};
+    std::vector<std::string> w;
+    for (int a = first; a < 3; a++)
+        if (with_fixed || m[a] != FIXED) { w.push_back(std::string("--boundary-") + "zyx"[a]); w.push_back(boundary_mode_name(m[a])); }
+    return w;
+}
+inline std::string joined(const std::vector<std::string> &w) { std::string s; for (auto &x : w) s += (s.empty() ? "" : " ") + x; return s; }
 
 struct Tap {
     int ds, dy, dx;     // offsets in (streamed, tile-row, tile-col) roles
@@ -220,7 +246,11 @@ struct KernelPlan {
     double drift_estimate = 0.0;     // predicted max relative distance from the fused arithmetic after the spec's iterations (0: gold order)
     double drift_per_launch = 0.0;   // the same after one launch (grows ~ launches^0.62)
     int horizon_iterations = -1;     // largest `iterations` for which the estimate stays within the bar (-1: unlimited, gold order)
-    bool periodic = false;   // --boundary periodic: every launch first fills the input's ring from its interior (wrap_<name>)
+    int bmode[3] = {FIXED, FIXED, FIXED};   // boundary mode per axis (z, y, x; z stays FIXED in 2D): --boundary and --boundary-z / -y / -x
+    bool periodic = false;   // every axis periodic (--boundary periodic, however spelled)
+    // some axis is not fixed: every launch first fills the input's ring on those axes from its interior (wrap_<name>)
+    bool fills_ring() const { return bmode[0] != FIXED || bmode[1] != FIXED || bmode[2] != FIXED; }
+    bool all_axes(int m) const { return (ndim == 2 || bmode[0] == m) && bmode[1] == m && bmode[2] == m; }
     bool second_order = false;   // --time-order 2: out = S(in) - out_old on the interior (out's interior is input, each cell's old value reaching only that cell)
     std::string error;       // non-empty: invalid configuration
     std::string note;        // non-empty: something the user asked for was not done (printed by the generator, kept in the banner)

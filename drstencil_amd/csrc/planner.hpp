@@ -266,9 +266,26 @@ inline KernelPlan make_plan(const Stencil &st, const GenOptions &o_in, const std
     p.NBY = p.has_y ? std::max(1, ceil_div(p.DY - H, p.OY)) : 1;
     p.NBS = p.has_s ? std::max(1, ceil_div(p.DS - 2 * H, p.SN)) : 1;
     if (p.DX - 2 * H < 1 || (p.has_y && p.DY - 2 * H < 1) || (p.has_s && p.DS - 2 * H < 1)) { p.error = "grid has no interior"; return p; }
-    // periodic: the period P = dim - 2 Halo must hold a ghost ring's worth of interior (P >= Halo), so that every ghost's source is interior
-    p.periodic = (o.boundary == "periodic");
-    if (p.periodic && (st.N < 3 * H || st.M < 3 * H || (st.ndim == 3 && st.L < 3 * H))) { p.error = "--boundary periodic needs every dimension >= 3 * Halo (period >= Halo)"; return p; }
+    // Non-fixed axes: the interior must hold a ghost ring's worth of cells (dim - 2 Halo >= Halo), so that every ghost's source is interior
+    // (periodic: the period P = dim - 2 Halo >= Halo; reflect: the mirror image of the ring stays inside the interior).  Fixed axes carry no
+    // such condition
+    for (int a = 0; a < 3; a++) p.bmode[a] = boundary_mode_of(o.axis_boundary(a));
+    if (st.ndim == 2) {
+        if (o.boundary_z_set && p.bmode[0] != FIXED) { p.error = std::string("--boundary-z ") + boundary_mode_name(p.bmode[0]) + ": a 2D grid has no z axis"; return p; }
+        p.bmode[0] = FIXED;
+    }
+    p.periodic = p.all_axes(PERIODIC);
+    if (p.periodic) {
+        if (st.N < 3 * H || st.M < 3 * H || (st.ndim == 3 && st.L < 3 * H)) { p.error = "--boundary periodic needs every dimension >= 3 * Halo (period >= Halo)"; return p; }
+    } else {
+        const int dim[3] = {st.L, st.M, st.N};
+        for (int a = 0; a < 3; a++)
+            if (p.bmode[a] != FIXED && dim[a] < 3 * H) {
+                p.error = joined(boundary_words(st.ndim, p.bmode, false)) + ": axis " + "zyx"[a] + " is " + boundary_mode_name(p.bmode[a]) + " and needs " + "LMN"[a] +
+                          " >= 3 * Halo (" + std::to_string(dim[a]) + " < " + std::to_string(3 * H) + ": a ghost's source must be interior)";
+                return p;
+            }
+    }
 
     // --time-order 2: one launch is one leapfrog step.  A fused S^n minus out_old is not n leapfrog steps, and on-chip stages are that too
     p.second_order = (o.time_order == 2);

@@ -36,12 +36,25 @@ import os
 import drstencil_amd as drs
 
 
+BOUNDARY_OPTIONS = ("--boundary", "--boundary-z", "--boundary-y", "--boundary-x")
+
+
 def refuse_periodic(opts, who):
-    """--boundary periodic has no slab form: the periodic outer faces would need a rank 0 <-> rank R-1 exchange."""
+    """A non-fixed boundary (--boundary periodic | reflect, or one axis through --boundary-z / -y / -x) has no slab form: periodic outer
+    faces would need a rank 0 <-> rank R-1 exchange, and a slab view's ring holds its neighbours' planes, which no view may refill."""
     opts = list(opts or ())
-    if any(a == "--boundary" and i + 1 < len(opts) and opts[i + 1] == "periodic" for i, a in enumerate(opts)):
+    given = [(a, opts[i + 1]) for i, a in enumerate(opts) if a in BOUNDARY_OPTIONS and i + 1 < len(opts) and (i == 0 or opts[i - 1] not in BOUNDARY_OPTIONS)]
+    mode = {}
+    for a, v in given:            # the last value wins; a per-axis option overrides --boundary wherever it stands
+        mode[a] = v
+    axes = [mode.get(a, mode.get("--boundary", "fixed")) for a in BOUNDARY_OPTIONS[1:]]
+    if all(m == "periodic" for m in axes):
         raise ValueError("%s: --boundary periodic is not supported by the slab decomposition (periodic z / y across ranks needs a "
                          "rank 0 <-> rank R-1 exchange); run it on one GPU" % who)
+    if any(m != "fixed" for m in axes):
+        named = " ".join("%s %s" % (a, v) for a, v in given if v != "fixed")
+        raise ValueError("%s: %s is not supported by the slab decomposition (it keeps every axis fixed: a slab view's ring holds its "
+                         "neighbours' planes); run it on one GPU" % (who, named))
 
 
 def refuse_second_order(opts, who):

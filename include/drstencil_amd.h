@@ -65,6 +65,9 @@ int drs_kernel_unload(drs_kernel *k);
  *   "out_skew_bytes", "placement_period_bytes": where the output array should sit relative to the input array, modulo the period
  *                                  (64 MiB): see drs_kernel_pair_layout below.
  *   "boundary": "periodic", "period": [P...]   only for kernels generated with --boundary periodic (see drs_kernel_wrap).
+ *   "boundary": "reflect" | "mixed", "boundaries": [modes, outermost axis first]   kernels with a reflecting axis or with axes of
+ *                                  different modes (--boundary reflect, --boundary-z / -y / -x): "fixed" | "periodic" | "reflect" per
+ *                                  axis, three entries in 3D, two in 2D.  Neither key: every axis is fixed.
  *   "time_order": 2                only for kernels generated with --time-order 2 (see drs_kernel_launch). */
 const char *drs_kernel_info(const drs_kernel *k);
 const char *drs_kernel_path(const drs_kernel *k);   /* the loaded shared object */
@@ -84,8 +87,8 @@ const char *drs_kernel_resources(const drs_kernel *k);
  * arena of *arena_bytes.  Advice only: every entry point accepts any two device pointers, results never depend on them. */
 int drs_kernel_pair_layout(const drs_kernel *k, size_t *arena_bytes, size_t *out_offset);
 /* one launch of dr_<name><<<grid, block, 0, stream>>>(in, out): codegen.hpp:577,582-583.
- * --boundary periodic kernels first run wrap_<name> on d_in (drs_kernel_wrap), so d_in's RING IS OVERWRITTEN although the
- * parameter is const; the result depends only on d_in's interior, and d_out's ring is not touched.  The same holds for
+ * Kernels with a non-fixed axis (--boundary periodic | reflect, --boundary-z / -y / -x) first run wrap_<name> on d_in
+ * (drs_kernel_wrap), so d_in's RING IS OVERWRITTEN ON ITS NON-FIXED AXES although the parameter is const; the result depends only on d_in's interior, and d_out's ring is not touched.  The same holds for
  * drs_kernel_launch_gold, drs_kernel_run and drs_kernel_run_timed, whose launches go through the same entry points.
  * --time-order 2 kernels compute d_out = S(d_in) - d_out on the interior: d_out's INTERIOR IS INPUT (each cell's old value reaches
  * only that cell; d_out's ring is neither read nor written).  The ping-pong loop of drs_kernel_run is then the leapfrog scheme
@@ -101,9 +104,15 @@ int drs_kernel_launch_gold(drs_kernel *k, const void *d_in, void *d_out, void *s
  * periodic domain of period P_d = dim_d - 2 * Halo in every dimension (Halo = step * order, so P depends on --step), and its ring
  * of width Halo holds ghost copies: the ghost at coordinate x takes the value at w(x) = x + P (x < Halo), x - P (x >= dim - Halo),
  * x otherwise, each coordinate wrapped on its own (edges and corners included).  One launch of wrap_<name> on d, asynchronous on
- * `stream`: fills d's ring from d's interior (the interior is not written).  -2 when the kernel was not generated with
- * --boundary periodic.  Such kernels need every dimension >= 3 * Halo; --gpus N > 1, --pair-launch 1 and the drs_slab_* runtime
- * refuse them. */
+ * `stream`: fills d's ring from d's interior (the interior is not written).
+ * --boundary reflect: zero-flux walls on the faces between ring and interior: the ghost takes m(x) = 2 Halo - 1 - x (x < Halo),
+ * 2 (dim - Halo) - 1 - x (x >= dim - Halo) -- the ghost at distance d outside a face is the interior cell at distance d - 1 inside
+ * (numpy's pad mode "symmetric").  --boundary-z / -y / -x choose the mode per axis; a fixed axis maps every coordinate to itself
+ * and its ring is never written.  A ring cell is filled iff one of its coordinates lies in the ring of a non-fixed axis, from the
+ * cell with every coordinate mapped on its own (which may lie in the ring of a fixed axis).  A fused --step n launch applies S^n
+ * to the mirrored extension: n mirrored one-step updates only for a one-step stencil symmetric along every reflecting axis.
+ * -2 when every axis of the kernel is fixed.  A non-fixed axis needs a dimension >= 3 * Halo; --gpus N > 1, --pair-launch 1 and
+ * the drs_slab_* runtime refuse every non-fixed axis. */
 int drs_kernel_wrap(drs_kernel *k, void *d, void *stream);
 /* the timed ping-pong loop: for (t = 0; t < iterations; t += 2*step) { k(A,B); k(B,A); }
  * (codegen.hpp:581-584).  gold != 0 runs gold_<name> instead.  Returns the number of

@@ -165,8 +165,27 @@ def host_lists():
     ]]
 
 
+def boundary_lists():
+    """--boundary reflect and --boundary-x / -y / -z.  Last in the corpus, so that the lists in front keep their numbers: against a build
+    without these options `diff -r` shows these files and nothing else."""
+    return [(None, l) for l in [
+        # reflecting and per-axis boundaries: vector and element rows, 2D, a fixed x, the canonical spelling, order 2 in a rigid box
+        ["--3d", "--dtype", "fp32", "--boundary", "reflect", "--check", stc("smoke3")],
+        ["--3d", "--dtype", "fp64", "--step", "2", "--boundary", "reflect", stc("t3_star_odd")],
+        ["--3d", "--dtype", "fp32", "--boundary-z", "fixed", "--boundary-y", "periodic", "--boundary-x", "reflect", stc("t3_star")],
+        ["--3d", "--dtype", "fp64", "--boundary", "reflect", "--boundary-x", "fixed", stc("t3_star")],
+        ["--3d", "--dtype", "fp32", "--boundary-x", "periodic", "--boundary-y", "periodic", "--boundary-z", "periodic", stc("t3_star")],
+        ["--dtype", "fp32", "--boundary-y", "periodic", "--boundary-x", "reflect", "--check", stc("t2_star")],
+        ["--dtype", "fp64", "--boundary", "reflect", stc("t2_odd")],
+        ["--3d", "--dtype", "fp32", "--time-order", "2", "--boundary", "reflect", stc("t3_wave")],
+        # rejected before the emitter is asked
+        ["--3d", "--boundary", "reflect", "--gpus", "2", stc("t3_star")], ["--3d", "--boundary-y", "periodic", "--pair-launch", "1", stc("t3_star")],
+        ["--boundary-z", "reflect", stc("t2_star")], ["--3d", "--boundary-x", "torus", stc("t3_star")],
+    ]] + [(None, j) for j in __import__("boundary_cases").all_build_args()]       # what build() emits for the boundary tests
+
+
 def corpus():
-    return build_lists() + space_sample() + host_lists() + knob_lists()
+    return build_lists() + space_sample() + host_lists() + knob_lists() + boundary_lists()
 
 
 def coverage(lists):

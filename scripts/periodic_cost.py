@@ -2,6 +2,7 @@
 with HIP events, alternating fixed / periodic, several repeats each.
 
     python scripts/periodic_cost.py --out profiles/periodic_cost.json            # C4 headline, C2 tile, c4f64 4-stage pipeline
+    python scripts/periodic_cost.py --boundary periodic reflect --out profiles/boundary_cost.json   # C4 headline and C2 tile, both modes in one run
     rocprofv3 --kernel-trace --stats -d TRACE -o c4 -- python scripts/periodic_cost.py --only c4 --repeats 2 --out /tmp/x.json
     python scripts/periodic_cost.py --summarize-trace TRACE --merge profiles/periodic_cost.json   # wrap kernel's own time (no GPU)
 
@@ -51,6 +52,12 @@ def verify(torch, kern, A0, A, B, Ag, Bg):
         Ag.copy_(A0)
         out["input_ring_is_wrap"] = bool(torch.equal(A, torch_wrap(Ag, H)))
         ok = ok and out["input_ring_is_wrap"]
+    elif kern.fills_ring:
+        from boundary_cases import host_fill
+        a = host_fill(A0.cpu().numpy(), H, kern.boundaries)          # on the host: the mirror reads reversed slices
+        out["input_ring_is_fill"] = bool(torch.equal(A.cpu(), torch.from_numpy(a)))
+        del a
+        ok = ok and out["input_ring_is_fill"]
     out["ok"] = bool(ok)
     return out
 
@@ -63,13 +70,20 @@ def measure(args):
     os.environ["DRS_NO_COMPILE"] = "1"
     dev = torch.device("cuda:0")
     rows = []
-    for cid, w, fixed_opts, per_opts in cost_cases():
+    modes = list(args.boundary)
+    cases = cost_cases()
+    if modes != ["periodic"]:       # the other modes are prebuilt for C4 headline and C2 tile (tests/boundary_cases.py)
+        import boundary_cases
+        cases = [c for c in cases if c[0] in [b[0] for b in boundary_cases.cost_cases()]]
+    for cid, w, fixed_opts, per_opts in cases:
         if args.only and cid not in args.only:
             continue
         wl = bench.WORKLOADS[w]
         kf = drs.Kernel(fixed_opts + [wl["stc"]])
-        kp = drs.Kernel(per_opts + [wl["stc"]])
-        assert kp.periodic and not kf.periodic
+        kern = {"fixed": kf}
+        for m in modes:
+            kern[m] = drs.Kernel(fixed_opts + ["--boundary", m, wl["stc"]])
+            assert kern[m].boundaries == (m,) * kf.info["ndim"] and not kf.fills_ring
         i = kf.info
         tdt = torch.float32 if i["dtype"] == "fp32" else torch.float64
         shape = (i["L"], i["M"], i["N"]) if i["ndim"] == 3 else (i["M"], i["N"])
@@ -77,12 +91,11 @@ def measure(args):
         g = torch.Generator(device=dev).manual_seed(1)
         A0 = torch.rand(shape, dtype=tdt, device=dev, generator=g)
         Ag, Bg = torch.empty_like(A0), torch.empty_like(A0)
-        checks = {"fixed": verify(torch, kf, A0, A, B, Ag, Bg), "periodic": verify(torch, kp, A0, A, B, Ag, Bg)}
+        checks = {name: verify(torch, k, A0, A, B, Ag, Bg) for name, k in kern.items()}
         del Ag, Bg
         step = i["step"]
         launches = args.launches
         stream = torch.cuda.current_stream(dev)
-        kern = {"fixed": kf, "periodic": kp}
 
         def loop(k):
             A.copy_(A0); B.zero_()
@@ -94,13 +107,14 @@ def measure(args):
             torch.cuda.synchronize()
             assert n == launches
             return e0.elapsed_time(e1) / n
-        for name in ("fixed", "periodic"):          # clocks up before anything is timed
+        names = ["fixed"] + modes
+        for name in names:          # clocks up before anything is timed
             t0 = time.perf_counter()
             while time.perf_counter() - t0 < MIN_WARM_S:
                 loop(kern[name])
-        ms = {"fixed": [], "periodic": []}
+        ms = {name: [] for name in names}
         for r in range(args.repeats):
-            for name in (("fixed", "periodic") if r % 2 == 0 else ("periodic", "fixed")):
+            for name in (names if r % 2 == 0 else names[::-1]):
                 ms[name].append(loop(kern[name]))
         ups = kf.updates_per_launch()
         med = {k: sorted(v)[len(v) // 2] for k, v in ms.items()}
@@ -108,19 +122,22 @@ def measure(args):
                "ms_per_launch": {k: [round(x, 5) for x in v] for k, v in ms.items()},
                "median_ms_per_launch": {k: round(v, 5) for k, v in med.items()},
                "gstencil_per_s": {k: round(ups / (v * 1e-3) / 1e9, 2) for k, v in med.items()},
-               "periodic_over_fixed_gstencil": round(med["fixed"] / med["periodic"], 4),
-               "wrap_ms_per_launch_by_difference": round(med["periodic"] - med["fixed"], 5),
+               "%s_over_fixed_gstencil" % modes[0]: round(med["fixed"] / med[modes[0]], 4),
+               "wrap_ms_per_launch_by_difference": round(med[modes[0]] - med["fixed"], 5),
                "ring_elements": int(A0.numel() - ups // step),
                "verified": checks}
+        for m in modes[1:]:
+            row["%s_over_fixed_gstencil" % m] = round(med["fixed"] / med[m], 4)
+        row["fixed_spread_ms"] = round(max(ms["fixed"]) - min(ms["fixed"]), 5)          # the fixed kernel's run-to-run spread in this run
         rows.append(row)
-        print(json.dumps({k: row[k] for k in ("id", "median_ms_per_launch", "gstencil_per_s", "periodic_over_fixed_gstencil", "verified")}), flush=True)
+        print(json.dumps({k: row[k] for k in ["id", "median_ms_per_launch", "gstencil_per_s", "fixed_spread_ms", "verified"] + ["%s_over_fixed_gstencil" % m for m in modes]}), flush=True)
         del A, B, arena, A0
         torch.cuda.empty_cache()
-    res = {"what": "fixed vs --boundary periodic, same sweep kernel, same arena, HIP events around run() of launches_per_loop launches, "
-                   "alternating fixed / periodic, input restored before every loop; median over repeats",
+    res = {"what": "fixed vs --boundary " + " / ".join(modes) + ", same sweep kernel, same arena, HIP events around run() of launches_per_loop launches, "
+                   "alternating the variants, input restored before every loop; median over repeats",
            "device": torch.cuda.get_device_name(0), "target": "C4 periodic >= 0.93 of fixed GStencil/s", "cases": rows}
     c4 = [r for r in rows if r["id"] == "c4"]
-    if c4:
+    if c4 and modes[0] == "periodic":
         res["c4_target_met"] = c4[0]["periodic_over_fixed_gstencil"] >= 0.93
     with open(args.out, "w") as f:
         json.dump(res, f, indent=1)
@@ -174,6 +191,8 @@ def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--out", default="periodic_cost.json")
     ap.add_argument("--only", nargs="*", help="case ids (c4, c2, c4f64_temporal4)")
+    ap.add_argument("--boundary", nargs="+", default=["periodic"], choices=["periodic", "reflect"],
+                    help="the non-fixed modes to time against fixed (default: periodic; `periodic reflect` times both in one run, C4 and C2)")
     ap.add_argument("--repeats", type=int, default=7)
     ap.add_argument("--launches", type=int, default=20, help="launches per timed loop (even; 20 x step 4 = 80 time steps stay finite in fp64, "
                                                               "20 x step 2 in fp32)")
