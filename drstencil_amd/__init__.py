@@ -64,6 +64,10 @@ def lib():
     L.drs_kernel_wrap.argtypes = [vp, vp, vp]
     L.drs_kernel_run.argtypes = [vp, vp, vp, ci, ci, vp]
     L.drs_kernel_run_timed.argtypes = [vp, vp, vp, ci, ci, vp, ctypes.POINTER(ctypes.c_float)]
+    L.drs_kernel_launch_src.argtypes = [vp, vp, vp, vp, vp]
+    L.drs_kernel_launch_gold_src.argtypes = [vp, vp, vp, vp, vp]
+    L.drs_kernel_run_src.argtypes = [vp, vp, vp, vp, ci, ci, vp]
+    L.drs_kernel_run_timed_src.argtypes = [vp, vp, vp, vp, ci, ci, vp, ctypes.POINTER(ctypes.c_float)]
     L.drs_slab_unique_id.argtypes = [vp]
     L.drs_slab_open.restype = vp
     L.drs_slab_open.argtypes = [ci, cpp, ci, cpp, ci, ci, ci, ci, ctypes.c_char_p, ctypes.POINTER(vp)]
@@ -94,6 +98,7 @@ EXPORTS = [
     "drs_spec_iterations", "drs_spec_launches", "drs_spec_dims", "drs_spec_point", "drs_spec_partition",
     "drs_kernel_build", "drs_kernel_close", "drs_kernel_unload", "drs_kernel_info", "drs_kernel_path", "drs_kernel_resources", "drs_kernel_pair_layout", "drs_kernel_launch", "drs_kernel_launch_pair",
     "drs_kernel_wrap", "drs_kernel_launch_gold", "drs_kernel_run", "drs_kernel_run_timed",
+    "drs_kernel_launch_src", "drs_kernel_launch_gold_src", "drs_kernel_run_src", "drs_kernel_run_timed_src",
     "drs_fill_random_f64", "drs_fill_random_f32", "drs_check_error_f64", "drs_check_error_f32",
     "drs_slab_unique_id", "drs_slab_open", "drs_slab_plan", "drs_slab_connect", "drs_slab_run", "drs_slab_sync", "drs_slab_stream", "drs_slab_info",
     "drs_slab_error", "drs_slab_close",
@@ -209,8 +214,19 @@ class Kernel:
         self.resources = json.loads(lib().drs_kernel_resources(self.h).decode() or "{}")   # registers / scratch / LDS per the compiler
         self.args = list(args)
 
-    def launch(self, d_in, d_out, stream=0):
-        rc = lib().drs_kernel_launch(self.h, d_in, d_out, stream)
+    def _src(self, d_src, who):
+        """The source array of a call, checked against the kernel: a --source kernel needs one, a plain kernel takes none."""
+        if self.source and not d_src:
+            raise ValueError("%s(): the kernel was generated with --source and needs d_src, the source array" % who)
+        if not self.source and d_src is not None:
+            raise ValueError("%s(): d_src given, but the kernel was generated without --source" % who)
+        return d_src
+
+    def launch(self, d_in, d_out, stream=0, d_src=None):
+        if self._src(d_src, "launch"):
+            rc = lib().drs_kernel_launch_src(self.h, d_in, d_out, d_src, stream)
+        else:
+            rc = lib().drs_kernel_launch(self.h, d_in, d_out, stream)
         if rc != 0:
             raise RuntimeError("HIP launch error %d" % rc)
 
@@ -245,6 +261,13 @@ class Kernel:
         interior is input too (the ping-pong loop of run() is then the leapfrog scheme u(t+1) = S(u(t)) - u(t-1)); else 1."""
         return int(self.info.get("time_order", 1))
 
+    @property
+    def source(self):
+        """True for kernels generated with --source: a launch takes a third, read-only array d_src of the grid's shape and computes
+        out = S(in) + src on the interior (with --time-order 2: (S(in) - out_old) + src); launch, launch_gold, run and run_timed then
+        need the keyword d_src, the same array for every launch of a loop."""
+        return bool(self.info.get("source", 0))
+
     def wrap(self, d, stream=0):
         """Kernels with a non-fixed axis (--boundary periodic | reflect, --boundary-x / -y / -z): fill the ring of width Halo of the device
         array `d` on those axes from its interior (periodic images one period, dim - 2 Halo, away; zero-flux mirror images about the face
@@ -256,15 +279,21 @@ class Kernel:
         if rc != 0:
             raise RuntimeError("HIP launch error %d" % rc)
 
-    def launch_gold(self, d_in, d_out, stream=0):
-        rc = lib().drs_kernel_launch_gold(self.h, d_in, d_out, stream)
+    def launch_gold(self, d_in, d_out, stream=0, d_src=None):
+        if self._src(d_src, "launch_gold"):
+            rc = lib().drs_kernel_launch_gold_src(self.h, d_in, d_out, d_src, stream)
+        else:
+            rc = lib().drs_kernel_launch_gold(self.h, d_in, d_out, stream)
         if rc != 0:
             raise RuntimeError("HIP launch error %d" % rc)
 
-    def run(self, d_a, d_b, iterations=None, gold=False, stream=0):
-        """The reference's ping-pong loop (codegen.hpp:581-584); result ends in A."""
+    def run(self, d_a, d_b, iterations=None, gold=False, stream=0, d_src=None):
+        """The reference's ping-pong loop (codegen.hpp:581-584); result ends in A.  --source kernels: the same d_src in every launch."""
         it = self.info["iterations"] if iterations is None else iterations
-        n = lib().drs_kernel_run(self.h, d_a, d_b, it, 1 if gold else 0, stream)
+        if self._src(d_src, "run"):
+            n = lib().drs_kernel_run_src(self.h, d_a, d_b, d_src, it, 1 if gold else 0, stream)
+        else:
+            n = lib().drs_kernel_run(self.h, d_a, d_b, it, 1 if gold else 0, stream)
         if n == -3:
             raise ToleranceHorizonExceeded(self._horizon_message(it))
         if n < 0:
@@ -293,11 +322,14 @@ class Kernel:
             out.append(("top", dim0 - nsl))
         return out
 
-    def run_timed(self, d_a, d_b, iterations=None, warmup=10, stream=0):
+    def run_timed(self, d_a, d_b, iterations=None, warmup=10, stream=0, d_src=None):
         """Warm-up launches + timed loop bracketed by HIP events on `stream`: (launches, ms)."""
         it = self.info["iterations"] if iterations is None else iterations
         ms = ctypes.c_float()
-        n = lib().drs_kernel_run_timed(self.h, d_a, d_b, it, warmup, stream, ctypes.byref(ms))
+        if self._src(d_src, "run_timed"):
+            n = lib().drs_kernel_run_timed_src(self.h, d_a, d_b, d_src, it, warmup, stream, ctypes.byref(ms))
+        else:
+            n = lib().drs_kernel_run_timed(self.h, d_a, d_b, it, warmup, stream, ctypes.byref(ms))
         if n == -3:
             raise ToleranceHorizonExceeded(self._horizon_message(it))
         if n < 0:
@@ -321,8 +353,8 @@ class Kernel:
     def bytes_per_launch(self):
         i = self.info
         pts = i["M"] * i["N"] * (i["L"] if i["ndim"] == 3 else 1)
-        # --time-order 2 also reads the old output: two reads and one write per point is the algorithmic minimum
-        return (3 if self.time_order == 2 else 2) * (4 if i["dtype"] == "fp32" else 8) * pts
+        # --time-order 2 also reads the old output, --source the source array: one more whole array each is the algorithmic minimum
+        return (2 + (self.time_order == 2) + self.source) * (4 if i["dtype"] == "fp32" else 8) * pts
 
     # ---- placement of the output array (csrc/schedule.hpp: Schedule::out_skew_bytes; profiles/r03_probe_skew4.log) ----
     def array_bytes(self):

@@ -34,6 +34,9 @@ struct drs_kernel {
     int (*launch)(const void *, void *, hipStream_t) = nullptr;
     int (*launch_gold)(const void *, void *, hipStream_t) = nullptr;
     int (*launch_pair)(const void *, void *, const void *, void *, hipStream_t) = nullptr;   // only with --pair-launch 1
+    // --source kernels take a third, read-only array: their plugins export these INSTEAD of launch / launch_gold
+    int (*launch_src)(const void *, void *, const void *, hipStream_t) = nullptr;
+    int (*launch_gold_src)(const void *, void *, const void *, hipStream_t) = nullptr;
     int (*wrap)(void *, hipStream_t) = nullptr;              // only with a non-fixed boundary (--boundary periodic / reflect, --boundary-x / -y / -z)
     const char *(*info)(void) = nullptr;
     std::string path;
@@ -339,6 +342,8 @@ drs_kernel *drs_kernel_build(int argc, const char *const *argv, const char *cach
     k->launch = (int (*)(const void *, void *, hipStream_t))dlsym(dl, "drs_plugin_launch");
     k->launch_gold = (int (*)(const void *, void *, hipStream_t))dlsym(dl, "drs_plugin_launch_gold");
     k->launch_pair = (int (*)(const void *, void *, const void *, void *, hipStream_t))dlsym(dl, "drs_plugin_launch_pair");
+    k->launch_src = (int (*)(const void *, void *, const void *, hipStream_t))dlsym(dl, "drs_plugin_launch_src");
+    k->launch_gold_src = (int (*)(const void *, void *, const void *, hipStream_t))dlsym(dl, "drs_plugin_launch_gold_src");
     k->wrap = (int (*)(void *, hipStream_t))dlsym(dl, "drs_plugin_wrap");
     k->info = (const char *(*)(void))dlsym(dl, "drs_plugin_info");
     k->path = so;
@@ -346,7 +351,10 @@ drs_kernel *drs_kernel_build(int argc, const char *const *argv, const char *cach
     k->step = r.st.step;
     k->horizon = r.plan.reassociated ? r.plan.horizon_iterations : -1;
     k->forced = r.plan.temporal_forced;
-    if (!k->launch || !k->launch_gold || !k->info) {
+    // either set of launch entry points, whole: the two-pointer one, or (--source) the three-pointer one
+    const bool plain = k->launch && k->launch_gold && !k->launch_src && !k->launch_gold_src;
+    const bool with_src = k->launch_src && k->launch_gold_src && !k->launch && !k->launch_gold;
+    if (!(plain || with_src) || with_src != r.plan.source || !k->info) {
         if (log) *log = dup_cstr("plugin " + so + " lacks the drs_plugin_* entry points\n");
         dlclose(dl);
         delete k;
@@ -389,6 +397,7 @@ int drs_kernel_pair_layout(const drs_kernel *k, size_t *arena_bytes, size_t *out
 }
 
 int drs_kernel_launch(drs_kernel *k, const void *d_in, void *d_out, void *stream) {
+    if (!k->launch) return -2;           // a --source kernel: drs_kernel_launch_src
     g_launched = true;
     return k->launch(d_in, d_out, (hipStream_t)stream);
 }
@@ -403,35 +412,49 @@ int drs_kernel_wrap(drs_kernel *k, void *d, void *stream) {
     return k->wrap(d, (hipStream_t)stream);
 }
 int drs_kernel_launch_gold(drs_kernel *k, const void *d_in, void *d_out, void *stream) {
+    if (!k->launch_gold) return -2;      // a --source kernel: drs_kernel_launch_gold_src
     g_launched = true;
     return k->launch_gold(d_in, d_out, (hipStream_t)stream);
 }
+int drs_kernel_launch_src(drs_kernel *k, const void *d_in, void *d_out, const void *d_src, void *stream) {
+    if (!k->launch_src || !d_src) return -2;      // the kernel was not generated with --source, or no source array
+    g_launched = true;
+    return k->launch_src(d_in, d_out, d_src, (hipStream_t)stream);
+}
+int drs_kernel_launch_gold_src(drs_kernel *k, const void *d_in, void *d_out, const void *d_src, void *stream) {
+    if (!k->launch_gold_src || !d_src) return -2;
+    g_launched = true;
+    return k->launch_gold_src(d_in, d_out, d_src, (hipStream_t)stream);
+}
 
-int drs_kernel_run(drs_kernel *k, void *d_a, void *d_b, int iterations, int gold, void *stream) {
-    auto fn = gold ? k->launch_gold : k->launch;
+// the ping-pong loop of both forms: d_src == nullptr on a kernel without --source, the source array of every launch on one with it
+static int run_loop(drs_kernel *k, void *d_a, void *d_b, const void *d_src, int iterations, int gold, void *stream) {
     // a temporal pipeline is only offered where it keeps the tolerance: more iterations than its horizon need the fused kernel
     // (or --temporal force, whose plugin says "temporal_forced" in drs_kernel_info)
     if (!gold && k->horizon >= 0 && !k->forced && iterations > k->horizon) return -3;
+    auto fn = gold ? k->launch_gold : k->launch;
+    auto fn_src = gold ? k->launch_gold_src : k->launch_src;
+    auto one = [&](const void *in, void *out) { return d_src ? fn_src(in, out, d_src, (hipStream_t)stream) : fn(in, out, (hipStream_t)stream); };
     g_launched = true;
     int n = 0;
     for (int t = 0; t < iterations; t += 2 * k->step) {
-        if (fn(d_a, d_b, (hipStream_t)stream) != 0) return -1;
-        if (fn(d_b, d_a, (hipStream_t)stream) != 0) return -1;
+        if (one(d_a, d_b) != 0) return -1;
+        if (one(d_b, d_a) != 0) return -1;
         n += 2;
     }
     return n;
 }
 
-int drs_kernel_run_timed(drs_kernel *k, void *d_a, void *d_b, int iterations, int warmup, void *stream, float *ms) {
+static int run_timed_loop(drs_kernel *k, void *d_a, void *d_b, const void *d_src, int iterations, int warmup, void *stream, float *ms) {
     hipStream_t s = (hipStream_t)stream;
     if (k->horizon >= 0 && !k->forced && iterations > k->horizon) return -3;      // as drs_kernel_run, before anything is launched
     g_launched = true;
     for (int i = 0; i < warmup; i++)
-        if (k->launch(d_a, d_b, s) != 0) return -1;
+        if ((d_src ? k->launch_src(d_a, d_b, d_src, s) : k->launch(d_a, d_b, s)) != 0) return -1;
     hipEvent_t e0, e1;
     if (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess) return -1;
     (void)hipEventRecord(e0, s);
-    int n = drs_kernel_run(k, d_a, d_b, iterations, 0, stream);
+    int n = run_loop(k, d_a, d_b, d_src, iterations, 0, stream);
     (void)hipEventRecord(e1, s);
     hipError_t err = hipEventSynchronize(e1);
     float t = 0.f;
@@ -440,6 +463,24 @@ int drs_kernel_run_timed(drs_kernel *k, void *d_a, void *d_b, int iterations, in
     (void)hipEventDestroy(e1);
     if (ms) *ms = t;
     return (err == hipSuccess) ? n : -1;
+}
+
+int drs_kernel_run(drs_kernel *k, void *d_a, void *d_b, int iterations, int gold, void *stream) {
+    if (!k->launch) return -2;           // a --source kernel: drs_kernel_run_src
+    return run_loop(k, d_a, d_b, nullptr, iterations, gold, stream);
+}
+int drs_kernel_run_src(drs_kernel *k, void *d_a, void *d_b, const void *d_src, int iterations, int gold, void *stream) {
+    if (!k->launch_src || !d_src) return -2;
+    return run_loop(k, d_a, d_b, d_src, iterations, gold, stream);
+}
+
+int drs_kernel_run_timed(drs_kernel *k, void *d_a, void *d_b, int iterations, int warmup, void *stream, float *ms) {
+    if (!k->launch) return -2;           // a --source kernel: drs_kernel_run_timed_src
+    return run_timed_loop(k, d_a, d_b, nullptr, iterations, warmup, stream, ms);
+}
+int drs_kernel_run_timed_src(drs_kernel *k, void *d_a, void *d_b, const void *d_src, int iterations, int warmup, void *stream, float *ms) {
+    if (!k->launch_src || !d_src) return -2;
+    return run_timed_loop(k, d_a, d_b, d_src, iterations, warmup, stream, ms);
 }
 
 // ---- inputs and error metric (common.hpp:9-102) -----------------------------------------------

@@ -26,7 +26,7 @@ inline std::string check_call(const KernelPlan &p, const std::string &outer) {
 inline std::string gold_kernel(const KernelPlan &p) {
     std::ostringstream g;
     g << "// naive reference kernel: the verification arithmetic (same term order, same FMA chain)\n";
-    g << "extern \"C\" __global__ void gold_" << p.name << " (const real_t* __restrict__ d_in, real_t* __restrict__ d_out)\n{\n";
+    g << "extern \"C\" __global__ void gold_" << p.name << " (const real_t* __restrict__ d_in, real_t* __restrict__ d_out" << (p.source ? ", const real_t* __restrict__ d_src" : "") << ")\n{\n";
     g << "    const int i = (int)(blockIdx.x * blockDim.x + threadIdx.x);\n";
     g << "    const int j = (int)(blockIdx.y * blockDim.y + threadIdx.y);\n";
     if (p.ndim == 3) g << "    const int k = (int)(blockIdx.z * blockDim.z + threadIdx.z);\n";
@@ -46,7 +46,10 @@ inline std::string gold_kernel(const KernelPlan &p) {
         first = false;
     }
     const std::string gidx = p.ndim == 3 ? "((long)k * M + j) * N + i" : "(long)j * N + i";
-    if (p.second_order) g << "        d_out[" << gidx << "] = t - d_out[" << gidx << "];\n";
+    if (p.source) {      // explicit statements: each a rounded operation of its own, in this order
+        if (p.second_order) g << "        t = t - d_out[" << gidx << "];\n";
+        g << "        d_out[" << gidx << "] = t + d_src[" << gidx << "];\n";
+    } else if (p.second_order) g << "        d_out[" << gidx << "] = t - d_out[" << gidx << "];\n";
     else g << "        d_out[" << gidx << "] = t;\n";
     g << "    }\n}\n\n";
     return g.str();
@@ -160,6 +163,7 @@ inline std::string info_json(const Schedule &s) {
                          p.SN, p.OX, p.OY, p.NBX, p.NBY, p.NBS, p.has_s ? 1 : 0,
                          (o.debug_drop_barrier || o.debug_skip) ? 0 : 1 /* 0: a timing experiment with barriers removed -- its results are wrong by design */);
     if (p.second_order) j.insert(j.size() - 1, ",\\\"time_order\\\":2");
+    if (p.source) j.insert(j.size() - 1, ",\\\"source\\\":1");
     if (p.periodic) {
         const int H = p.halo;
         j.insert(j.size() - 1, p.ndim == 3 ? sfmt(",\\\"boundary\\\":\\\"periodic\\\",\\\"period\\\":[%d,%d,%d]", p.L - 2 * H, p.M - 2 * H, p.N - 2 * H)
@@ -184,18 +188,20 @@ inline std::string plugin_api(const Schedule &s) {
         a << "    return (int)hipGetLastError();\n}\n";
     }
     const std::string wrap_in = p.fills_ring() ? "    if (int rc = drs_plugin_wrap((void*)in, stream)) return rc;\n" : "";
-    a << "extern \"C\" int drs_plugin_launch(const void* in, void* out, hipStream_t stream)\n{\n" << wrap_in;
-    a << "    hipLaunchKernelGGL(dr_" << p.name << ", dim3(DRS_GRID), dim3(DRS_NTL), 0, stream, (const real_t*)in, (real_t*)out);\n";
+    // --source kernels take three arrays: they export the _src entry points INSTEAD of the two-pointer ones
+    const std::string sfx = p.source ? "_src" : "", src_par = p.source ? ", const void* src" : "", src_arg = p.source ? ", (const real_t*)src" : "";
+    a << "extern \"C\" int drs_plugin_launch" << sfx << "(const void* in, void* out" << src_par << ", hipStream_t stream)\n{\n" << wrap_in;
+    a << "    hipLaunchKernelGGL(dr_" << p.name << ", dim3(DRS_GRID), dim3(DRS_NTL), 0, stream, (const real_t*)in, (real_t*)out" << src_arg << ");\n";
     a << "    return (int)hipGetLastError();\n}\n";
     if (o.pair_launch) {
         a << "extern \"C\" int drs_plugin_launch_pair(const void* in0, void* out0, const void* in1, void* out1, hipStream_t stream)\n{\n";
         a << "    hipLaunchKernelGGL(dr2_" << p.name << ", dim3(DRS_GRID, 2), dim3(DRS_NTL), 0, stream, (const real_t*)in0, (real_t*)out0, (const real_t*)in1, (real_t*)out1);\n";
         a << "    return (int)hipGetLastError();\n}\n";
     }
-    a << "extern \"C\" int drs_plugin_launch_gold(const void* in, void* out, hipStream_t stream)\n{\n" << wrap_in;
+    a << "extern \"C\" int drs_plugin_launch_gold" << sfx << "(const void* in, void* out" << src_par << ", hipStream_t stream)\n{\n" << wrap_in;
     if (p.ndim == 3) a << "    dim3 b(64, 2, 2), g((N + 63) / 64, (M + 1) / 2, (L + 1) / 2);\n";
     else a << "    dim3 b(64, 4, 1), g((N + 63) / 64, (M + 3) / 4, 1);\n";
-    a << "    hipLaunchKernelGGL(gold_" << p.name << ", g, b, 0, stream, (const real_t*)in, (real_t*)out);\n";
+    a << "    hipLaunchKernelGGL(gold_" << p.name << ", g, b, 0, stream, (const real_t*)in, (real_t*)out" << src_arg << ");\n";
     a << "    return (int)hipGetLastError();\n}\n";
     a << "extern \"C\" const char* drs_plugin_info(void)\n{\n    return \"" << info_json(s) << "\";\n}\n\n";
     return a.str();
@@ -587,21 +593,32 @@ inline std::string host_main(const Schedule &s) {
     h << "    const size_t npoints = " << dims << ";\n    const size_t nbytes = sizeof(real_t) * npoints;\n";
     if (p.second_order) h << "    real_t* h_in = getRandomArray<real_t> (npoints);\n    real_t* h_out = getRandomArray<real_t> (npoints);   // time order 2: out holds u(t-1), input too (the rand() sequence continued)\n";
     else h << "    real_t* h_in = getRandomArray<real_t> (npoints);\n    real_t* h_out = getZeroArray<real_t> (npoints);\n";
+    // --source: the third array continues the reference's rand() fill behind the arrays filled today; it lies behind the pair in the same arena
+    const std::string launch = p.source ? "drs_plugin_launch_src" : "drs_plugin_launch", gold = p.source ? "drs_plugin_launch_gold_src" : "drs_plugin_launch_gold";
+    const std::string sarg = p.source ? ", src" : "";
+    if (p.source) h << "    real_t* h_src = getRandomArray<real_t> (npoints);   // the source term (the rand() sequence continued)\n";
     h << "    // both arrays in ONE allocation, the output " << (s.out_skew_bytes() >> 20) << " MiB (mod " << (Schedule::kPlacementPeriod >> 20) << " MiB) behind the input: launch time depends on (out - in) mod 64 MiB (--out-skew)\n";
     h << "    const size_t out_at = (nbytes + " << Schedule::kPlacementPeriod - 1 << "UL) / " << Schedule::kPlacementPeriod << "UL * " << Schedule::kPlacementPeriod << "UL + " << s.out_skew_bytes() << "UL;\n";
+    if (p.source)
+        h << "    const size_t src_at = (out_at + nbytes + 255UL) / 256UL * 256UL;   // the source array behind the pair\n"
+             "    char *arena;\n    (void)hipMalloc (&arena, src_at + nbytes);\n    check_error (\"Failed to allocate device memory for in, out and src.\\n\");\n"
+             "    real_t *in = (real_t*)arena, *out = (real_t*)(arena + out_at);\n    const real_t *src = (const real_t*)(arena + src_at);\n"
+             "    (void)hipMemcpy (in, h_in, nbytes, hipMemcpyHostToDevice);\n    (void)hipMemcpy (out, h_out, nbytes, hipMemcpyHostToDevice);\n"
+             "    (void)hipMemcpy (arena + src_at, h_src, nbytes, hipMemcpyHostToDevice);\n\n";
+    else
     h << "    char *arena;\n    (void)hipMalloc (&arena, out_at + nbytes);\n    check_error (\"Failed to allocate device memory for in and out.\\n\");\n"
          "    real_t *in = (real_t*)arena, *out = (real_t*)(arena + out_at);\n"
          "    (void)hipMemcpy (in, h_in, nbytes, hipMemcpyHostToDevice);\n    (void)hipMemcpy (out, h_out, nbytes, hipMemcpyHostToDevice);\n\n";
-    h << "    puts(\"GPU computing ...\");\n\n    // warm up\n    for (int i = 0; i < 10; i ++) drs_plugin_launch (in, out, 0);\n\n";
+    h << "    puts(\"GPU computing ...\");\n\n    // warm up\n    for (int i = 0; i < 10; i ++) " << launch << " (in, out" << sarg << ", 0);\n\n";
     if (p.second_order)
         h << "    // time order 2: a launch reads its output, so the warm-up has advanced the state: both arrays start the timed (and checked) sequence afresh\n"
              "    (void)hipMemcpy (in, h_in, nbytes, hipMemcpyHostToDevice);\n    (void)hipMemcpy (out, h_out, nbytes, hipMemcpyHostToDevice);\n\n";
     h << "    hipEvent_t ev0, ev1;\n    (void)hipEventCreate (&ev0); (void)hipEventCreate (&ev1);\n    int launches = 0;\n    (void)hipEventRecord (ev0, 0);\n";
-    h << "    for (int t = 0; t < Iterations; t += " << 2 * p.step << ") {\n        drs_plugin_launch (in, out, 0);\n        drs_plugin_launch (out, in, 0);\n        launches += 2;\n    }\n";
+    h << "    for (int t = 0; t < Iterations; t += " << 2 * p.step << ") {\n        " << launch << " (in, out" << sarg << ", 0);\n        " << launch << " (out, in" << sarg << ", 0);\n        launches += 2;\n    }\n";
     h << "    (void)hipEventRecord (ev1, 0);\n    (void)hipDeviceSynchronize();\n    check_error (\"Kernel error\");\n    float ms = 0.f;\n    (void)hipEventElapsedTime (&ms, ev0, ev1);\n";
     h << "    puts(\"GPU finished computing.\");\n    printf(\"GPU computation time: %f ms\\n\", ms);\n";
     h << "    {\n        const double updates = (double)launches * Step * " << interior_expr(p) << ";\n"
-         "        const double bytes = (double)launches * " << (p.second_order ? "3.0" : "2.0") << " * sizeof(real_t) * (double)npoints;\n"
+         "        const double bytes = (double)launches * " << sfmt("%d.0", 2 + s.extra_streams()) << " * sizeof(real_t) * (double)npoints;\n"
          "        if (launches > 0 && ms > 0.f) {\n"
          "            printf(\"[Perf] %.3f GStencil/s, %d launches\\n\", updates / (ms * 1e-3) / 1e9, launches);\n"
          "            printf(\"[Perf] achieved %.1f GB/s = %.1f %% of the MI355X HBM3E roofline (8000 GB/s)\\n\", bytes / (ms * 1e-3) / 1e9, bytes / (ms * 1e-3) / 8e12 * 100.0);\n"
@@ -610,12 +627,13 @@ inline std::string host_main(const Schedule &s) {
         h << "\n    // run the gold kernel and check error\n    puts (\"Checking error ...\");\n    real_t *g_in, *g_out;\n"
              "    (void)hipMalloc (&g_in, nbytes);\n    check_error (\"Failed to allocate device memory for g_in.\\n\");\n    (void)hipMemcpy (g_in, h_in, nbytes, hipMemcpyHostToDevice);\n"
              "    (void)hipMalloc (&g_out, nbytes);\n    check_error (\"Failed to allocate device memory for g_out.\\n\");\n    (void)hipMemcpy (g_out, h_out, nbytes, hipMemcpyHostToDevice);\n";
-        h << "    for (int t = 0; t < Iterations; t += " << 2 * p.step << ") {\n        drs_plugin_launch_gold (g_in, g_out, 0);\n        drs_plugin_launch_gold (g_out, g_in, 0);\n    }\n";
+        h << "    for (int t = 0; t < Iterations; t += " << 2 * p.step << ") {\n        " << gold << " (g_in, g_out" << sarg << ", 0);\n        " << gold << " (g_out, g_in" << sarg << ", 0);\n    }\n";
         h << "    (void)hipDeviceSynchronize();\n    check_error (\"Kernel(gold) error\");\n    real_t* h_g_out = h_in;   // reuse the memory of the input array\n"
              "    (void)hipMemcpy (h_out, in, nbytes, hipMemcpyDeviceToHost);\n    (void)hipMemcpy (h_g_out, g_in, nbytes, hipMemcpyDeviceToHost);\n";
         h << "    double error = " << check_call(p, p.ndim == 3 ? "h_out, h_g_out, Halo, L-Halo" : "h_out, h_g_out, Halo, M-Halo") << ";\n";
         h << "    printf(\"[Test] RMS Error: %e\\n\", error);\n    (void)hipFree (g_in);\n    (void)hipFree (g_out);\n";
     }
+    if (p.source) h << "\n    delete[] h_src;";
     h << "\n    delete[] h_in;\n    delete[] h_out;\n    (void)hipFree (arena);\n    return 0;\n}\n#endif\n";
     return h.str();
 }

@@ -128,6 +128,13 @@ MI355X options:
                         OUTPUT array's interior is input too (its ring is neither read nor written).  S(in) is the same FMA chain,
                         rounded once; the subtraction is one more rounded operation.  Needs --step 1; not with --temporal,
                         --gpus N > 1 or --pair-launch 1.
+--source                A per-cell source term: a launch takes a third array src of the grid's shape and dtype and computes
+                        out = S(in) + src on the interior (Jacobi for Poisson's equation: u <- avg(u) + h^2/2d f; a heat source; a
+                        forcing of the wave equation).  With --time-order 2: out = (S(in) - out_old) + src.  S(in) is the same FMA
+                        chain, rounded once; the addition is one more rounded operation.  src is read in the interior only and never
+                        written; it must not overlap out; the same src goes to every launch of the ping-pong loop.  The kernel is
+                        dr_<name>(in, out, src) and the plugin exports drs_plugin_launch_src / drs_plugin_launch_gold_src.  Needs
+                        --step 1; not with --temporal, --gpus N > 1 or --pair-launch 1.
 --xrim <lds|dpp>        x halo inside a wavefront by DPP wave shifts (default) or through LDS.
 --schedule <scatter|reuse|window>  How reuse along the streamed dimension is split between source planes kept on chip and
                         partial sums carried in VGPRs (results never depend on it):
@@ -266,7 +273,7 @@ inline constexpr Opt kOptions[] = {
     {"--boundary-x", &GenOptions::boundary_x, "fixed periodic reflect", NAMES, &GenOptions::boundary_x_set},
     {"--boundary-y", &GenOptions::boundary_y, "fixed periodic reflect", NAMES, &GenOptions::boundary_y_set},
     {"--boundary-z", &GenOptions::boundary_z, "fixed periodic reflect", NAMES, &GenOptions::boundary_z_set},
-    {"--time-order", &GenOptions::time_order, NAMES},
+    {"--time-order", &GenOptions::time_order, NAMES}, {"--source", &GenOptions::source, NAMES},
     {"--gpus", &GenOptions::gpus, NAMES | LOCAL}, {"--pair-launch", &GenOptions::pair_launch, NAMES}, {"--temporal", put_temporal, NAMES},
     {"--out-skew", &GenOptions::out_skew, NAMES}, {"--tuned-defaults", &GenOptions::tuned_defaults, NAMES},
     {"--schedule", &GenOptions::schedule, "scatter reuse window", 0, &GenOptions::schedule_set},
@@ -416,6 +423,13 @@ inline GenResult generate(const std::vector<std::string> &args /* argv[1..] */) 
                                     : "--time-order 2 cannot be combined with --pair-launch 1 (the pair kernel serves the slab runtime, which has no second-order form)";
         return res;
     }
+    if (res.plan.source && (o.gpus > 1 || o.pair_launch)) {
+        // the slab views are windows of two arrays; a view of the source array is no part of the slab runtime, and the pair kernel serves it
+        res.messages += "Invalid configuration!\n"; res.exit_code = 255;
+        res.error = o.gpus > 1 ? "--source cannot be combined with --gpus N > 1 (the slab runtime passes no view of a source array)"
+                               : "--source cannot be combined with --pair-launch 1 (the pair kernel serves the slab runtime, which has no source term)";
+        return res;
+    }
     const Schedule sched(res.plan, o);
     if (!sched.config_error().empty()) { res.messages += "Invalid configuration!\n"; res.exit_code = 255; res.error = sched.config_error(); return res; }
     if (sched.lds_bytes() > 160 * 1024) {   // gfx950: 160 KiB of LDS per workgroup
@@ -453,6 +467,9 @@ inline GenResult generate(const std::vector<std::string> &args /* argv[1..] */) 
     }
     if (res.plan.second_order)
         res.notes += "drstencil: note: second-order time stepping: a launch computes out = S(in) - out_old on the interior (the output array's interior is input)\n";
+    if (res.plan.source)
+        res.notes += std::string("drstencil: note: source term: a launch takes a third array and computes out = ") +
+                     (res.plan.second_order ? "(S(in) - out_old) + src" : "S(in) + src") + " on the interior (src is read only, in its interior)\n";
     if (!res.tuned_from.empty())
         res.notes += "drstencil: note: no geometry option given: the tuner's configuration for this stencil, step, dtype and grid size is used (" +
                      res.tuned_from + "); --tuned-defaults 0 keeps the generic defaults\n";

@@ -181,6 +181,10 @@ struct GenOptions {
     int time_order = 1;          // --time-order 2: a launch computes out = S(in) - out_old on the interior (the leapfrog update of a second-order
                                  // equation, u(t+1) = S(u(t)) - u(t-1): the ping-pong loop k(A,B); k(B,A) is then leapfrog as it stands).  The old
                                  // output is a third memory stream of the sweep, read once.  It names the problem, not a tuning choice
+    bool source = false;         // --source: a launch takes a third, read-only array src of the grid's shape and computes out = S(in) + src on the
+                                 // interior (a Jacobi sweep for Poisson's equation, a heat source, a forcing term of the wave equation); with
+                                 // --time-order 2, out = (S(in) - out_old) + src.  src is one more memory stream of the sweep, read once.  It names
+                                 // the problem, not a tuning choice
 };
 
 // ---- boundary modes per axis (0 z, 1 y, 2 x; z counts as fixed in 2D)
@@ -252,6 +256,7 @@ struct KernelPlan {
     bool fills_ring() const { return bmode[0] != FIXED || bmode[1] != FIXED || bmode[2] != FIXED; }
     bool all_axes(int m) const { return (ndim == 2 || bmode[0] == m) && bmode[1] == m && bmode[2] == m; }
     bool second_order = false;   // --time-order 2: out = S(in) - out_old on the interior (out's interior is input, each cell's old value reaching only that cell)
+    bool source = false;         // --source: out = S(in) + src (order 2: (S(in) - out_old) + src) on the interior; src's interior is read, each value reaching only its own cell
     std::string error;       // non-empty: invalid configuration
     std::string note;        // non-empty: something the user asked for was not done (printed by the generator, kept in the banner)
 };

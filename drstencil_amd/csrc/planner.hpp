@@ -291,6 +291,10 @@ inline KernelPlan make_plan(const Stencil &st, const GenOptions &o_in, const std
     p.second_order = (o.time_order == 2);
     if (p.second_order && o_in.step > 1) { p.error = "--time-order 2 needs --step 1 (a fused S^n minus the old output is not n leapfrog steps)"; return p; }
     if (p.second_order && o_in.temporal) { p.error = "--time-order 2 cannot be combined with --temporal (on-chip stages fuse time steps; leapfrog needs the old output of every step)"; return p; }
+    // --source: one launch is one forced step.  S^n(in) + f is not n forced steps (f would have to pass through n - 1 sweeps), fused or staged
+    p.source = o.source;
+    if (p.source && o_in.step > 1) { p.error = "--source needs --step 1 (a fused S^n plus the source is not n forced steps)"; return p; }
+    if (p.source && o_in.temporal) { p.error = "--source cannot be combined with --temporal (on-chip stages fuse time steps; every forced step adds the source)"; return p; }
 
     if (o.loader_waves > 0 && o.stage != "dma") { p.error = "--loader-waves goes with --stage dma"; return p; }
     if (o.stage == "dma") {

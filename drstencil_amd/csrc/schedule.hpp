@@ -78,14 +78,17 @@ struct Schedule {
     // 32-bit registers of the per-lane state the kernel names: partial sums, register windows (own points + rims) and the
     // prefetch sets.  The tuner's FilterParams compares it with the register file a lane can have at the workgroup's size
     // (drstencil_amd/tuner/tuning.py: fitted against the compiler's resource reports, profiles/r02_reg_model.md).
-    int reg_demand() const { return reg_demand_sweep() + (p.second_order ? (p.fp32 ? 1 : 2) * old_sets() * p.RY * p.VX : 0); }
+    int reg_demand() const { return reg_demand_sweep() + (p.fp32 ? 1 : 2) * extra_streams() * old_sets() * p.RY * p.VX; }
     // ---- --time-order 2: the old output, the sweep's third memory stream -----------------------------------------------------------
     // out = S(in) - out_old.  The old vector of every (r, q) the lane stores is loaded into named registers ov<set>_<r>_<q>, under the
     // store's own guards, old_dist() planes AHEAD of the iteration that completes and stores that plane: with --prefetch at the prefetch
     // distance, next to the source-plane loads (its latency runs under PD planes of LDS exchange, barriers and FMAs), else at the top of
     // the plane's own iteration, in front of the LDS write and the barrier.  The sets rotate by renaming (the unroll is a multiple of
     // PD + 1).  The value is read once: a non-temporal load.  emit_final subtracts it from the finished sums in place.
-    int old_dist() const { return (p.second_order && p.prefetch && p.has_s && !p.dma) ? PD : 0; }
+    // ---- --source: the source term is one more stream of the same kind, from a third array: out = S(in) + src, or (S(in) - out_old) + src.
+    // Both extra read streams share the distance and each has its own family of old_dist() + 1 register sets (sv<set>_<r>_<q> beside ov...).
+    int extra_streams() const { return (p.second_order ? 1 : 0) + (p.source ? 1 : 0); }
+    int old_dist() const { return (extra_streams() && p.prefetch && p.has_s && !p.dma) ? PD : 0; }
     int old_sets() const { return old_dist() + 1; }
     int reg_demand_sweep() const {
         const int words = p.fp32 ? 1 : 2, pts = p.RY * p.VX;

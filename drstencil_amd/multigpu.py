@@ -65,6 +65,12 @@ def refuse_second_order(opts, who):
                          "valid old values); run it on one GPU" % who)
 
 
+def refuse_source(opts, who):
+    """--source has no slab form: the slab classes pass views of two arrays, none of a source array."""
+    if "--source" in list(opts or ()):
+        raise ValueError("%s: --source is not supported by the slab decomposition (it passes no view of a source array); run it on one GPU" % who)
+
+
 def slab_bounds(L, world, rank):
     """Planes [z0, z1) owned by `rank` (balanced split of the outermost dim)."""
     return (rank * L) // world, ((rank + 1) * L) // world
@@ -309,7 +315,9 @@ class HipSweep:
         refuse_periodic(opts, "HipSweep")
         refuse_periodic(alone_opts, "HipSweep")
         refuse_second_order(opts, "HipSweep")
+        refuse_source(opts, "HipSweep")
         refuse_second_order(alone_opts, "HipSweep")
+        refuse_source(alone_opts, "HipSweep")
         self.base_stc, self.opts, self.cache_dir = base_stc, list(opts), cache_dir
         self.alone_opts = list(alone_opts) if alone_opts else None
         self.ndim = 3 if "--3d" in self.opts else 2
@@ -424,6 +432,7 @@ class SlabRun:
         exchange (1 or 2, see SlabPlan)."""
         refuse_periodic(getattr(sweep, "opts", None), "SlabRun")
         refuse_second_order(getattr(sweep, "opts", None), "SlabRun")
+        refuse_source(getattr(sweep, "opts", None), "SlabRun")
         self.torch, self.dist = torch, dist
         dims = tuple(dims)
         self.plan = SlabPlan(dims[0], H, world, rank, every if world > 1 else 1)
@@ -615,7 +624,9 @@ class NativeSlabRun:
         refuse_periodic(opts, "NativeSlabRun")
         refuse_periodic(alone_opts, "NativeSlabRun")
         refuse_second_order(opts, "NativeSlabRun")
+        refuse_source(opts, "NativeSlabRun")
         refuse_second_order(alone_opts, "NativeSlabRun")
+        refuse_source(alone_opts, "NativeSlabRun")
         self.torch, self.dist = torch, dist
         dims = tuple(dims)
         pworld = rehearse_world or world

@@ -68,7 +68,8 @@ int drs_kernel_unload(drs_kernel *k);
  *   "boundary": "reflect" | "mixed", "boundaries": [modes, outermost axis first]   kernels with a reflecting axis or with axes of
  *                                  different modes (--boundary reflect, --boundary-z / -y / -x): "fixed" | "periodic" | "reflect" per
  *                                  axis, three entries in 3D, two in 2D.  Neither key: every axis is fixed.
- *   "time_order": 2                only for kernels generated with --time-order 2 (see drs_kernel_launch). */
+ *   "time_order": 2                only for kernels generated with --time-order 2 (see drs_kernel_launch).
+ *   "source": 1                    only for kernels generated with --source (see drs_kernel_launch_src). */
 const char *drs_kernel_info(const drs_kernel *k);
 const char *drs_kernel_path(const drs_kernel *k);   /* the loaded shared object */
 /* JSON: vgprs, agprs, sgprs, scratch_bytes_per_lane, sgpr_spill, vgpr_spill, occupancy_waves_per_simd, lds_bytes of
@@ -123,6 +124,20 @@ int drs_kernel_run(drs_kernel *k, void *d_a, void *d_b, int iterations, int gold
  * HIP events recorded on `stream`; blocks until done; *ms = elapsed milliseconds.  With a --time-order 2 kernel the warm-up
  * launches ADVANCE THE STATE (each reads and rewrites d_b's interior): restore both arrays afterwards if the values matter. */
 int drs_kernel_run_timed(drs_kernel *k, void *d_a, void *d_b, int iterations, int warmup, void *stream, float *ms);
+
+/* ---- --source kernels: a third, read-only operand ---------------------------------------------------------------------------------
+ * A kernel generated with --source is dr_<name>(in, out, src): d_out = S(d_in) + d_src on the interior, and with --time-order 2
+ * d_out = (S(d_in) - d_out) + d_src, each operation rounded on its own.  d_src has the grid's shape and dtype; only its INTERIOR is read,
+ * each value reaching only its own cell, and it is never written.  It must not overlap d_out (it may be d_in); it follows the
+ * alignment rule of the other two arrays.  Its plugin exports the three-pointer launch entry points INSTEAD of the two-pointer ones:
+ * drs_kernel_launch, _launch_gold, _run and _run_timed return -2 on such a kernel, and the four below return -2 on a kernel
+ * generated without --source and on a null d_src.  The loops pass the same d_src to every launch: k(A,B,F); k(B,A,F).  Everything said
+ * of the two-pointer forms (ring fill on d_in first, warm-up of an order-2 kernel advancing the state, -3 beyond a tolerance horizon)
+ * holds unchanged; --step n > 1, --temporal, --gpus N > 1, --pair-launch 1 and the drs_slab_* runtime refuse --source. */
+int drs_kernel_launch_src(drs_kernel *k, const void *d_in, void *d_out, const void *d_src, void *stream);
+int drs_kernel_launch_gold_src(drs_kernel *k, const void *d_in, void *d_out, const void *d_src, void *stream);
+int drs_kernel_run_src(drs_kernel *k, void *d_a, void *d_b, const void *d_src, int iterations, int gold, void *stream);
+int drs_kernel_run_timed_src(drs_kernel *k, void *d_a, void *d_b, const void *d_src, int iterations, int warmup, void *stream, float *ms);
 
 /* ---- N > 1: one rank of a slab-decomposed run (z slabs in 3D, y slabs in 2D), one process per GPU -----------------------------
  * No reference counterpart: the reference is single-GPU (no cudaSetDevice / streams / NCCL anywhere; SURVEY.md section 5 sketches

@@ -184,8 +184,32 @@ def boundary_lists():
     ]] + [(None, j) for j in __import__("boundary_cases").all_build_args()]       # what build() emits for the boundary tests
 
 
+def source_lists():
+    """--source.  Behind everything else, so that the lists in front keep their numbers: against a build without the option `diff -r`
+    shows these files (and --help) and nothing else."""
+    import source_cases
+    src3 = ["--3d", "--dtype", "fp32", "--source", "--check"]
+    lists = [
+        # the emitted main() with a third array, every issue point of the stream, both extra streams at once, the knob bases
+        src3 + [stc("t3_wave")], src3 + ["--store-mask", "buffer", stc("t3_wave")],
+        src3 + ["--prefetch", "--prefetch-depth", "2", stc("t3_wave")], src3 + ["--prefetch", "--prefetch-depth", "2", "--store-mask", "buffer", stc("t3_wave")],
+        src3 + ["--time-order", "2", "--prefetch", "--prefetch-depth", "2", stc("t3_wave")], src3 + ["--stage", "dma", stc("t3_wave")],
+        src3 + ["--order", "rows", "--pack", "1", "--block-merge-x", "4", "--defer-stores", "1", "--prefetch", stc("t3_wave")],
+        ["--dtype", "fp64", "--source", "--time-order", "2", "--check", stc("t2_wave")], ["--dtype", "fp32", "--source", "--boundary", "reflect", stc("t2_star")],
+        ["--dtype", "fp64", "--source", "--streaming", "--stage", "dma", stc("t2_star")],
+        # rejected before the emitter is asked
+        ["--3d", "--source", "--step", "2", stc("t3_star")], ["--3d", "--source", "--step", "2", "--temporal", "1", stc("t3_star")],
+        ["--3d", "--source", "--temporal", "force", stc("t3_star")], ["--3d", "--source", "--gpus", "2", stc("t3_star")],
+        ["--3d", "--source", "--pair-launch", "1", stc("t3_star")],
+    ]
+    for b in ("d3f64", "tile", "cross", "stream"):
+        opts, name = BASES[b]
+        lists.append(list(opts) + ["--source", stc(name)])
+    return [(None, l) for l in lists] + [(None, j) for j in source_cases.all_build_args()]       # what build() emits for the source tests
+
+
 def corpus():
-    return build_lists() + space_sample() + host_lists() + knob_lists() + boundary_lists()
+    return build_lists() + space_sample() + host_lists() + knob_lists() + boundary_lists() + source_lists()
 
 
 def coverage(lists):
