@@ -4,6 +4,8 @@ or fused, odd lane counts, both dtypes) on small ragged grids, each compared wit
 bit for bit for single-pass kernels, within the dtype's bar for temporal pipelines.
 --mode periodic | order2 | order2_periodic (or FUZZ_MODE) draws the same space with --boundary periodic and / or --time-order 2 and
 checks against the oracle with the host wrap in front of every launch / followed by the subtraction of the old output.
+--mode reflect | mixed | source | order2_source: --boundary reflect, a seeded per-axis boundary triple, --source, --time-order 2
+--source, against boundary_cases.oracle_boundary_run / source_cases.host_run (tests/options_reference.py).
 Builds everything before HIP is initialised."""
 import os, random, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))   # tests/ may use the oracle as the checker
@@ -83,19 +85,29 @@ def round4_knobs(rnd, cl):
     return cl
 
 
-MODES = ("fixed", "periodic", "order2", "order2_periodic")
+MODES = ("fixed", "periodic", "order2", "order2_periodic", "reflect", "mixed", "source", "order2_source")
 # the new problem modes draw over the small specs of the periodic and order-2 suites: (ndim, spec, order)
 MODE_STCS = [(3, "t3_star", 1), (3, "t3_star_odd", 1), (3, "t3_cross", 1), (3, "t3_odd", 1), (3, "t3_wave", 1),
              (2, "t2_star", 1), (2, "t2_box25", 2), (2, "t2_odd", 1), (2, "t2_wave", 1)]
 MODE_OPTS = {"fixed": [], "periodic": ["--boundary", "periodic"], "order2": ["--time-order", "2"],
-             "order2_periodic": ["--time-order", "2", "--boundary", "periodic"]}
+             "order2_periodic": ["--time-order", "2", "--boundary", "periodic"],
+             "reflect": ["--boundary", "reflect"], "mixed": [],         # mixed: a per-axis triple drawn per job (boundary_cases.mode_triple)
+             "source": ["--source"], "order2_source": ["--time-order", "2", "--source"]}
+STEP1_MODES = ("order2", "order2_periodic", "source", "order2_source")      # what the generator accepts there: step 1, no on-chip stages
 MODE = os.environ.get("FUZZ_MODE", "fixed")             # the manual sweeps' mode (fuzz_parity.py / fuzz_shapes.py; --mode on the command line wins)
 
 
 def job_mode(args):
-    """The problem mode a job's argument list names."""
+    """The problem mode a job's argument list names.  --source jobs are "source" / "order2_source" whatever their boundaries (their
+    reference takes the per-axis modes from the arguments), every other job with a reflecting or per-axis boundary "reflect" / "mixed"."""
     per = "--boundary" in args and args[args.index("--boundary") + 1] == "periodic"
     o2 = "--time-order" in args and args[args.index("--time-order") + 1] == "2"
+    if "--source" in args:
+        return "order2_source" if o2 else "source"
+    if any(a in args for a in ("--boundary-x", "--boundary-y", "--boundary-z")):
+        return "mixed"
+    if "--boundary" in args and args[args.index("--boundary") + 1] == "reflect":
+        return "reflect"
     return "order2_periodic" if per and o2 else "order2" if o2 else "periodic" if per else "fixed"
 
 
@@ -123,7 +135,7 @@ def make_jobs(n, seed, mode="fixed"):
         rnd, stcs = random, STCS
     else:
         rnd, stcs = random.Random("%s/%d" % (mode, seed)), MODE_STCS
-    order2 = mode.startswith("order2")
+    order2 = mode in STEP1_MODES
     jobs = []
     pair = 0
     for ndim, name, order in stcs:
@@ -173,7 +185,12 @@ def make_jobs(n, seed, mode="fixed"):
                         round4_knobs(rnd, cl)
                         if "--skew" in cl and ndim == 2 and "--streaming" not in cl:
                             del cl[cl.index("--skew"):cl.index("--skew") + 2]          # one-shot 2D tiles have no stream to skew
-                args = (["--3d"] if ndim == 3 else []) + ["--dtype", dtype] + cl + MODE_OPTS[mode] + [stc]
+                extra = MODE_OPTS[mode]
+                if mode == "mixed":                # drawn last: the earlier draws of a job are those of the other modes' generators
+                    import boundary_cases
+                    spec = oracle.Spec(stc, ndim, v[0])
+                    extra = boundary_cases.mode_triple(rnd, ndim, [d >= 3 * spec.halo for d in spec.shape])
+                args = (["--3d"] if ndim == 3 else []) + ["--dtype", dtype] + cl + extra + [stc]
                 if mode != "fixed" and not t.registerFilter(args):
                     continue
                 taken += 1
@@ -200,8 +217,10 @@ def mode_inputs(spec, dtype, temporal):
 def mode_reference(spec, A, B, launches, mode):
     """The host reference of `launches` launches of the ping-pong loop in `mode`, in place: the oracle's contracted sweep (fixed),
     with the host wrap in front of every launch (periodic_cases.oracle_periodic_run), or followed by one subtraction of the old output
-    (wave_cases.host_run, with the wrap where the mode is periodic too)."""
+    (wave_cases.host_run, with the wrap where the mode is periodic too).  The modes whose reference needs the job's own options (a
+    per-axis triple, a source array) go through tests/options_reference.py."""
     import periodic_cases, wave_cases
+    assert mode in ("fixed", "periodic", "order2", "order2_periodic"), mode
     if mode.startswith("order2"):
         return wave_cases.host_run(spec, A, B, launches, periodic=mode == "order2_periodic")
     if mode == "periodic":
@@ -243,7 +262,11 @@ def compare_mode_run(spec, mode, dtype, A0, B0, A, B, Ar, Br, launches, temporal
 
 def check_mode(job, k, torch, mode):
     """check() for the periodic / order-2 modes: Kernel.run for the spec's iterations from random A and random B against
-    mode_reference, then the gold kernel from the same inputs against the same reference (always bit for bit)."""
+    mode_reference, then the gold kernel from the same inputs against the same reference (always bit for bit).  The reflect / mixed /
+    source / order2_source modes go through options_reference.check_options."""
+    if mode in ("reflect", "mixed", "source", "order2_source"):
+        from options_reference import check_options
+        return check_options(job, k, torch)
     ndim, stc, dtype, args, step = job
     temporal = k.info.get("stages", 1) > 1
     assert not (temporal and mode != "periodic"), "an order-2 kernel with on-chip stages"
@@ -296,7 +319,7 @@ def check(job, k, torch):
 
 
 def main():
-    mode = mode_from_argv(sys.argv)                   # fuzz_parity.py [--mode periodic | order2 | order2_periodic] <n> <seed>
+    mode = mode_from_argv(sys.argv)                   # fuzz_parity.py [--mode periodic | order2 | order2_periodic | reflect | mixed | source | order2_source] <n> <seed>
     n = int(sys.argv[1]) if len(sys.argv) > 1 else 120
     jobs = make_jobs(n, int(sys.argv[2]) if len(sys.argv) > 2 else 1, mode)
     t0 = time.time()

@@ -5,11 +5,14 @@ orders 1-3, on small ragged grids, each with a few random configurations from th
 and some illegal --dist) and compared with the CPU oracle like tests/fuzz_parity.py: bit for bit for single-pass kernels,
 within the dtype's bar for temporal pipelines.  The hand-written test stencils are stars, boxes and crosses; this sweep is
 for everything else the .stc format can say.
-usage: fuzz_shapes.py [--mode periodic | order2 | order2_periodic] <shapes> <configurations per shape and dtype> <seed>.
+usage: fuzz_shapes.py [--mode periodic | order2 | order2_periodic | reflect | mixed | source | order2_source] <shapes> <configurations per shape and dtype> <seed>.
 FUZZ_BUILD_ONLY=1 fills the kernel cache on a box without a GPU (the .stc files are regenerated from the seed on either side).
 --mode (or FUZZ_MODE) adds --boundary periodic and / or --time-order 2 to every configuration (fuzz_parity.check then compares with
 the mode's host reference): periodic configurations whose grid is smaller than 3 Halo of the drawn step in some dimension are skipped
-(the generator would reject them: a legal refusal, not a finding), order 2 keeps to step 1 without on-chip stages."""
+(the generator would reject them: a legal refusal, not a finding), order 2 keeps to step 1 without on-chip stages.  --mode reflect
+(--boundary reflect, skipped on small grids like periodic), mixed (a seeded per-axis triple; axes shorter than 3 Halo stay fixed), source
+and order2_source (--source, step 1 like order 2) likewise.  The fixed sample of shapes x modes that the test suite runs is
+tests/shape_mode_cases.py."""
 import itertools, os, random, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))   # tests/ may use the oracle as the checker
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
@@ -18,6 +21,7 @@ from drstencil_amd.tuner import tuning as t
 from helpers import write_stc
 from concurrent.futures import ProcessPoolExecutor
 import fuzz_parity as fp
+from shape_knobs import config_options, legal_dists      # shared with the suite's fixed sample (tests/shape_mode_cases.py)
 
 BIG = bool(os.environ.get("FUZZ_SHAPES_BIG"))
 dropped = [0]         # configurations the tuner's spill model kept from the compiler
@@ -53,17 +57,6 @@ def random_shape(rnd, ndim, h):
     return pts, mixed
 
 
-def legal_dists(pts, step):
-    """The --dist values for which the reference finds data to reuse (drstencil.hpp:198-259): some point of the fused
-    stencil has another one `dist` behind it along the outermost dimension."""
-    offs = {p[:-1] for p in pts}
-    fused = {tuple([0] * len(next(iter(offs))))}
-    for _ in range(step):
-        fused = {tuple(a + b for a, b in zip(f, o)) for f in fused for o in offs}
-    span = max(f[0] for f in fused) - min(f[0] for f in fused)
-    return [d for d in range(1, span + 1) if any((f[0] - d,) + f[1:] in fused for f in fused)]
-
-
 def make_jobs(nshapes, per, seed, mode="fixed"):
     assert mode in fp.MODES and not (BIG and mode != "fixed"), mode      # check_gold knows the fixed boundary only
     rnd = random.Random(seed)
@@ -83,50 +76,24 @@ def make_jobs(nshapes, per, seed, mode="fixed"):
         write_stc(stc, ndim, dims, rnd.randint(1, 7), pts)     # iterations: 2 * ceil(iterations / (2 * step)) launches (codegen.hpp:581-584)
         distinct = len(set(p[:-1] for p in pts))
         steps = tuple(st for st in (1, 2, 3) if min((2 * h * st + 1) ** ndim, distinct ** st) <= MAX_TAPS)
-        if mode.startswith("order2"):
+        if mode in fp.STEP1_MODES:
             steps = (1,)                         # what the generator accepts with --time-order 2 (no --temporal at step 1 either)
         dists = {}
         for dtype in ("fp32", "fp64"):
             t.order, t.ndim, t.elem_bytes = h, ndim, 4 if dtype == "fp32" else 8
             space = t.enumerate_space(steps)
             for v in rnd.sample(space, min(len(space), per)):
-                cl = t.cfgToCommandLine(v).split()
-                if "--temporal" in cl and mixed:
-                    continue                     # a relative bar means nothing where the sum cancels
-                r = rnd.random()
-                i = cl.index("--dist")
-                legal = dists.setdefault(v[0], legal_dists(pts, v[0]))
-                if r < 0.2:                      # the reference's range, (step-1)*order .. step*order (tuning.py:20): refused ("No data to reuse") or right
-                    cl[i + 1] = str(rnd.randint(max(1, (v[0] - 1) * h), v[0] * h))
-                elif r < 0.4 and legal:          # a distance this shape has data to reuse at
-                    cl[i + 1] = str(rnd.choice(legal))
-                elif r < 0.45:                   # anything: must be refused or right
-                    cl[i + 1] = str(rnd.randint(1, 2 * v[0] * h + 1))
-                elif r < 0.6:                    # the default, (high - low) / 2
-                    del cl[i:i + 2]
-                if ndim == 2 and rnd.random() < 0.5:
-                    cl.append("--streaming")
-                if "--prefetch-depth" in cl:
-                    cl[cl.index("--prefetch-depth") + 1] = str(rnd.choice([1, 2, 3, 4]))
-                if "--schedule" not in cl and rnd.random() < 0.6:
-                    cl[cl.index("--merge-forward") + 1] = str(rnd.choice([0, 2, 3, 100]))
-                if rnd.random() < 0.2:
-                    cl += ["--uniform-loads", str(rnd.choice([1, 2]))]
-                if rnd.random() < 0.2:
-                    cl += ["--store-mask", "buffer"]
-                if rnd.random() < 0.25 and "--temporal" not in cl and "--cyclic-merge-y" not in cl and (ndim == 3 or "--streaming" in cl):
-                    cl += ["--stage", "dma"]
-                if rnd.random() < 0.2:
-                    cl += ["--defer-stores", "1"]
-                if fp.ROUND3:
-                    fp.round3_knobs(rnd, cl)
-                    fp.round4_knobs(rnd, cl)
-                    if "--skew" in cl and ndim == 2 and "--streaming" not in cl:
-                        del cl[cl.index("--skew"):cl.index("--skew") + 2]
-                if mode.endswith("periodic") and min(dims[3 - ndim:]) < 3 * h * v[0]:
-                    skipped_small[0] += 1        # --boundary periodic needs every dimension >= 3 Halo (Halo = step * order)
+                cl = config_options(rnd, v, ndim, h, pts, mixed, dists)
+                if cl is None:
                     continue
-                args = (["--3d"] if ndim == 3 else []) + ["--dtype", dtype] + cl + fp.MODE_OPTS[mode] + [stc]
+                if (mode.endswith("periodic") or mode == "reflect") and min(dims[3 - ndim:]) < 3 * h * v[0]:
+                    skipped_small[0] += 1        # --boundary periodic | reflect needs every dimension >= 3 Halo (Halo = step * order)
+                    continue
+                extra = fp.MODE_OPTS[mode]
+                if mode == "mixed":              # drawn last
+                    import boundary_cases
+                    extra = boundary_cases.mode_triple(rnd, ndim, [d >= 3 * h * v[0] for d in dims[3 - ndim:]])
+                args = (["--3d"] if ndim == 3 else []) + ["--dtype", dtype] + cl + extra + [stc]
                 if not t.registerFilter(args):   # the tuner's spill model: do not compile what would be refused for scratch
                     dropped[0] += 1
                     continue
@@ -168,7 +135,7 @@ def main():
     per = int(sys.argv[2]) if len(sys.argv) > 2 else 6
     jobs = make_jobs(nshapes, per, int(sys.argv[3]) if len(sys.argv) > 3 else 1, mode)
     if skipped_small[0]:
-        print("%d periodic configurations skipped: grid smaller than 3 Halo of the drawn step" % skipped_small[0])
+        print("%d periodic / reflecting configurations skipped: grid smaller than 3 Halo of the drawn step" % skipped_small[0])
     t0 = time.time()
     with ProcessPoolExecutor(max_workers=int(os.environ.get("FUZZ_JOBS", "16"))) as ex:
         errs = list(ex.map(fp.build, jobs, chunksize=4))
