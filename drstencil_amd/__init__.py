@@ -68,6 +68,13 @@ def lib():
     L.drs_kernel_launch_gold_src.argtypes = [vp, vp, vp, vp, vp]
     L.drs_kernel_run_src.argtypes = [vp, vp, vp, vp, ci, ci, vp]
     L.drs_kernel_run_timed_src.argtypes = [vp, vp, vp, vp, ci, ci, vp, ctypes.POINTER(ctypes.c_float)]
+    L.drs_kernel_residual_elems.restype = ctypes.c_long
+    L.drs_kernel_residual_elems.argtypes = [vp]
+    L.drs_kernel_launch_res.argtypes = [vp, vp, vp, vp, vp, vp]
+    L.drs_kernel_run_res.argtypes = [vp, vp, vp, vp, vp, ci, vp]
+    L.drs_kernel_run_timed_res.argtypes = [vp, vp, vp, vp, vp, ci, ci, vp, ctypes.POINTER(ctypes.c_float)]
+    L.drs_kernel_residual.argtypes = [vp, vp, ctypes.POINTER(ctypes.c_double)]
+    L.drs_kernel_solve.argtypes = [vp, vp, vp, vp, vp, ctypes.c_double, ci, ci, vp, ctypes.POINTER(ci), ctypes.POINTER(ctypes.c_double)]
     L.drs_slab_unique_id.argtypes = [vp]
     L.drs_slab_open.restype = vp
     L.drs_slab_open.argtypes = [ci, cpp, ci, cpp, ci, ci, ci, ci, ctypes.c_char_p, ctypes.POINTER(vp)]
@@ -99,6 +106,7 @@ EXPORTS = [
     "drs_kernel_build", "drs_kernel_close", "drs_kernel_unload", "drs_kernel_info", "drs_kernel_path", "drs_kernel_resources", "drs_kernel_pair_layout", "drs_kernel_launch", "drs_kernel_launch_pair",
     "drs_kernel_wrap", "drs_kernel_launch_gold", "drs_kernel_run", "drs_kernel_run_timed",
     "drs_kernel_launch_src", "drs_kernel_launch_gold_src", "drs_kernel_run_src", "drs_kernel_run_timed_src",
+    "drs_kernel_residual_elems", "drs_kernel_launch_res", "drs_kernel_run_res", "drs_kernel_run_timed_res", "drs_kernel_residual", "drs_kernel_solve",
     "drs_fill_random_f64", "drs_fill_random_f32", "drs_check_error_f64", "drs_check_error_f32",
     "drs_slab_unique_id", "drs_slab_open", "drs_slab_plan", "drs_slab_connect", "drs_slab_run", "drs_slab_sync", "drs_slab_stream", "drs_slab_info",
     "drs_slab_error", "drs_slab_close",
@@ -222,8 +230,47 @@ class Kernel:
             raise ValueError("%s(): d_src given, but the kernel was generated without --source" % who)
         return d_src
 
-    def launch(self, d_in, d_out, stream=0, d_src=None):
-        if self._src(d_src, "launch"):
+    def _res(self, d_res, who):
+        """The residual array of a call, checked against the kernel: a --residual kernel needs one, any other kernel takes none."""
+        if self.residual_elems and not d_res:
+            raise ValueError("%s(): the kernel was generated with --residual and needs d_res, an array of residual_elems elements" % who)
+        if not self.residual_elems and d_res is not None:
+            raise ValueError("%s(): d_res given, but the kernel was generated without --residual" % who)
+        return d_res
+
+    @property
+    def residual_elems(self):
+        """Elements of the residual array of a kernel generated with --residual max (1 + launched workgroups, of the grid's dtype; every
+        launch writes all of them, the caller initialises none); 0 for a kernel without the option.  launch, run and run_timed of such a
+        kernel need the keyword d_res; d_res[0] then holds the last launch's max |out - in| over the interior (residual())."""
+        return int(lib().drs_kernel_residual_elems(self.h))
+
+    def residual(self, d_res):
+        """d_res[0] of a --residual kernel as a Python float (the device is synchronised by the copy): the residual of the last launch."""
+        if not self._res(d_res, "residual"):
+            raise ValueError("residual(): the kernel was generated without --residual")
+        v = ctypes.c_double()
+        if lib().drs_kernel_residual(self.h, d_res, ctypes.byref(v)) != 0:
+            raise RuntimeError("HIP error reading the residual")
+        return float(v.value)
+
+    def solve(self, d_a, d_b, d_res, tol, max_launches, check_every=8, d_src=None, stream=0):
+        """Run to tolerance (drs_kernel_solve): ping-pong pairs k(A,B); k(B,A), `check_every` pairs between two looks at the residual, until
+        it is <= tol.  (status, launches, residual): status 0 converged, 1 max_launches (rounded down to an even number) reached, -4 the
+        residual is NaN or inf (a diverged or overflowed run).  The answer is in A."""
+        self._res(d_res, "solve")
+        n, r = ctypes.c_int(), ctypes.c_double()
+        rc = lib().drs_kernel_solve(self.h, d_a, d_b, self._src(d_src, "solve"), d_res, tol, max_launches, check_every, stream, ctypes.byref(n), ctypes.byref(r))
+        if rc == -2:
+            raise ValueError("solve(): the kernel was generated without --residual, or check_every < 1")
+        if rc == -1:
+            raise RuntimeError("HIP error in drs_kernel_solve")
+        return rc, n.value, r.value
+
+    def launch(self, d_in, d_out, stream=0, d_src=None, d_res=None):
+        if self._res(d_res, "launch"):
+            rc = lib().drs_kernel_launch_res(self.h, d_in, d_out, self._src(d_src, "launch"), d_res, stream)
+        elif self._src(d_src, "launch"):
             rc = lib().drs_kernel_launch_src(self.h, d_in, d_out, d_src, stream)
         else:
             rc = lib().drs_kernel_launch(self.h, d_in, d_out, stream)
@@ -287,10 +334,23 @@ class Kernel:
         if rc != 0:
             raise RuntimeError("HIP launch error %d" % rc)
 
-    def run(self, d_a, d_b, iterations=None, gold=False, stream=0, d_src=None):
-        """The reference's ping-pong loop (codegen.hpp:581-584); result ends in A.  --source kernels: the same d_src in every launch."""
+    def run(self, d_a, d_b, iterations=None, gold=False, stream=0, d_src=None, d_res=None):
+        """The reference's ping-pong loop (codegen.hpp:581-584); result ends in A.  --source kernels: the same d_src in every launch.
+        --residual kernels: d_res[0] then holds the last launch's residual (the gold kernel computes none: gold=True takes no d_res)."""
         it = self.info["iterations"] if iterations is None else iterations
-        if self._src(d_src, "run"):
+        if gold and self.residual_elems:
+            # gold_<name> keeps its entry point: the loop is made of single launches
+            if d_res is not None:
+                raise ValueError("run(): the gold kernel computes no residual")
+            n = 0
+            for t in range(0, it, 2 * self.info["step"]):
+                self.launch_gold(d_a, d_b, stream, d_src)
+                self.launch_gold(d_b, d_a, stream, d_src)
+                n += 2
+            return n
+        if self._res(d_res, "run"):
+            n = lib().drs_kernel_run_res(self.h, d_a, d_b, self._src(d_src, "run"), d_res, it, stream)
+        elif self._src(d_src, "run"):
             n = lib().drs_kernel_run_src(self.h, d_a, d_b, d_src, it, 1 if gold else 0, stream)
         else:
             n = lib().drs_kernel_run(self.h, d_a, d_b, it, 1 if gold else 0, stream)
@@ -322,11 +382,13 @@ class Kernel:
             out.append(("top", dim0 - nsl))
         return out
 
-    def run_timed(self, d_a, d_b, iterations=None, warmup=10, stream=0, d_src=None):
+    def run_timed(self, d_a, d_b, iterations=None, warmup=10, stream=0, d_src=None, d_res=None):
         """Warm-up launches + timed loop bracketed by HIP events on `stream`: (launches, ms)."""
         it = self.info["iterations"] if iterations is None else iterations
         ms = ctypes.c_float()
-        if self._src(d_src, "run_timed"):
+        if self._res(d_res, "run_timed"):
+            n = lib().drs_kernel_run_timed_res(self.h, d_a, d_b, self._src(d_src, "run_timed"), d_res, it, warmup, stream, ctypes.byref(ms))
+        elif self._src(d_src, "run_timed"):
             n = lib().drs_kernel_run_timed_src(self.h, d_a, d_b, d_src, it, warmup, stream, ctypes.byref(ms))
         else:
             n = lib().drs_kernel_run_timed(self.h, d_a, d_b, it, warmup, stream, ctypes.byref(ms))
@@ -353,7 +415,8 @@ class Kernel:
     def bytes_per_launch(self):
         i = self.info
         pts = i["M"] * i["N"] * (i["L"] if i["ndim"] == 3 else 1)
-        # --time-order 2 also reads the old output, --source the source array: one more whole array each is the algorithmic minimum
+        # --time-order 2 also reads the old output, --source the source array: one more whole array each is the algorithmic minimum (the centre
+        # values of --residual are cells the sweep reads anyway)
         return (2 + (self.time_order == 2) + self.source) * (4 if i["dtype"] == "fp32" else 8) * pts
 
     # ---- placement of the output array (csrc/schedule.hpp: Schedule::out_skew_bytes; profiles/r03_probe_skew4.log) ----

@@ -37,6 +37,10 @@ struct drs_kernel {
     // --source kernels take a third, read-only array: their plugins export these INSTEAD of launch / launch_gold
     int (*launch_src)(const void *, void *, const void *, hipStream_t) = nullptr;
     int (*launch_gold_src)(const void *, void *, const void *, hipStream_t) = nullptr;
+    // --residual kernels: ONE sweep entry point with every array in its signature (src null unless --source), INSTEAD of launch / launch_src
+    int (*launch_res)(const void *, void *, const void *, void *, hipStream_t) = nullptr;
+    long residual_elems = 0;     // elements of d_res (1 + launched workgroups); 0: no --residual
+    bool has_source = false, fp32 = false;
     int (*wrap)(void *, hipStream_t) = nullptr;              // only with a non-fixed boundary (--boundary periodic / reflect, --boundary-x / -y / -z)
     const char *(*info)(void) = nullptr;
     std::string path;
@@ -344,6 +348,10 @@ drs_kernel *drs_kernel_build(int argc, const char *const *argv, const char *cach
     k->launch_pair = (int (*)(const void *, void *, const void *, void *, hipStream_t))dlsym(dl, "drs_plugin_launch_pair");
     k->launch_src = (int (*)(const void *, void *, const void *, hipStream_t))dlsym(dl, "drs_plugin_launch_src");
     k->launch_gold_src = (int (*)(const void *, void *, const void *, hipStream_t))dlsym(dl, "drs_plugin_launch_gold_src");
+    k->launch_res = (int (*)(const void *, void *, const void *, void *, hipStream_t))dlsym(dl, "drs_plugin_launch_res");
+    k->has_source = r.plan.source;
+    k->fp32 = r.plan.fp32;
+    k->residual_elems = r.plan.residual ? Schedule(r.plan, r.opt).residual_elems() : 0;
     k->wrap = (int (*)(void *, hipStream_t))dlsym(dl, "drs_plugin_wrap");
     k->info = (const char *(*)(void))dlsym(dl, "drs_plugin_info");
     k->path = so;
@@ -351,9 +359,13 @@ drs_kernel *drs_kernel_build(int argc, const char *const *argv, const char *cach
     k->step = r.st.step;
     k->horizon = r.plan.reassociated ? r.plan.horizon_iterations : -1;
     k->forced = r.plan.temporal_forced;
-    // either set of launch entry points, whole: the two-pointer one, or (--source) the three-pointer one
-    const bool plain = k->launch && k->launch_gold && !k->launch_src && !k->launch_gold_src;
-    const bool with_src = k->launch_src && k->launch_gold_src && !k->launch && !k->launch_gold;
+    // either set of launch entry points, whole: the two-pointer one, or (--source) the three-pointer one; with --residual the sweep's entry
+    // point of either set gives way to drs_plugin_launch_res and the gold one stays
+    const bool with_res = r.plan.residual;
+    const bool sweep_plain = with_res ? (k->launch_res && !k->launch && !k->launch_src) : (k->launch && !k->launch_src && !k->launch_res);
+    const bool sweep_src = with_res ? sweep_plain : (k->launch_src && !k->launch && !k->launch_res);
+    const bool plain = sweep_plain && k->launch_gold && !k->launch_gold_src;
+    const bool with_src = sweep_src && k->launch_gold_src && !k->launch_gold;
     if (!(plain || with_src) || with_src != r.plan.source || !k->info) {
         if (log) *log = dup_cstr("plugin " + so + " lacks the drs_plugin_* entry points\n");
         dlclose(dl);
@@ -427,6 +439,15 @@ int drs_kernel_launch_gold_src(drs_kernel *k, const void *d_in, void *d_out, con
     return k->launch_gold_src(d_in, d_out, d_src, (hipStream_t)stream);
 }
 
+long drs_kernel_residual_elems(const drs_kernel *k) { return k ? k->residual_elems : 0; }
+// the source array of a --residual call, checked against the kernel: a --source kernel needs one, a kernel without it takes none
+static bool res_args_ok(const drs_kernel *k, const void *d_src, const void *d_res) { return k->launch_res && d_res && (k->has_source ? d_src != nullptr : d_src == nullptr); }
+int drs_kernel_launch_res(drs_kernel *k, const void *d_in, void *d_out, const void *d_src, void *d_res, void *stream) {
+    if (!res_args_ok(k, d_src, d_res)) return -2;      // the kernel was not generated with --residual, no residual array, or a source array that does not go with the kernel
+    g_launched = true;
+    return k->launch_res(d_in, d_out, d_src, d_res, (hipStream_t)stream);
+}
+
 // the ping-pong loop of both forms: d_src == nullptr on a kernel without --source, the source array of every launch on one with it
 static int run_loop(drs_kernel *k, void *d_a, void *d_b, const void *d_src, int iterations, int gold, void *stream) {
     // a temporal pipeline is only offered where it keeps the tolerance: more iterations than its horizon need the fused kernel
@@ -481,6 +502,75 @@ int drs_kernel_run_timed(drs_kernel *k, void *d_a, void *d_b, int iterations, in
 int drs_kernel_run_timed_src(drs_kernel *k, void *d_a, void *d_b, const void *d_src, int iterations, int warmup, void *stream, float *ms) {
     if (!k->launch_src || !d_src) return -2;
     return run_timed_loop(k, d_a, d_b, d_src, iterations, warmup, stream, ms);
+}
+
+// ---- --residual kernels: the loops with the residual array, and the run to tolerance -----------------------------------------------------
+static int run_loop_res(drs_kernel *k, void *d_a, void *d_b, const void *d_src, void *d_res, int iterations, void *stream) {
+    g_launched = true;
+    int n = 0;
+    for (int t = 0; t < iterations; t += 2 * k->step) {
+        if (k->launch_res(d_a, d_b, d_src, d_res, (hipStream_t)stream) != 0) return -1;
+        if (k->launch_res(d_b, d_a, d_src, d_res, (hipStream_t)stream) != 0) return -1;
+        n += 2;
+    }
+    return n;
+}
+int drs_kernel_run_res(drs_kernel *k, void *d_a, void *d_b, const void *d_src, void *d_res, int iterations, void *stream) {
+    if (!res_args_ok(k, d_src, d_res)) return -2;
+    return run_loop_res(k, d_a, d_b, d_src, d_res, iterations, stream);
+}
+int drs_kernel_run_timed_res(drs_kernel *k, void *d_a, void *d_b, const void *d_src, void *d_res, int iterations, int warmup, void *stream, float *ms) {
+    if (!res_args_ok(k, d_src, d_res)) return -2;
+    hipStream_t s = (hipStream_t)stream;
+    g_launched = true;
+    for (int i = 0; i < warmup; i++)
+        if (k->launch_res(d_a, d_b, d_src, d_res, s) != 0) return -1;
+    hipEvent_t e0, e1;
+    if (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess) return -1;
+    (void)hipEventRecord(e0, s);
+    const int n = run_loop_res(k, d_a, d_b, d_src, d_res, iterations, stream);
+    (void)hipEventRecord(e1, s);
+    hipError_t err = hipEventSynchronize(e1);
+    float t = 0.f;
+    if (err == hipSuccess) err = hipEventElapsedTime(&t, e0, e1);
+    (void)hipEventDestroy(e0);
+    (void)hipEventDestroy(e1);
+    if (ms) *ms = t;
+    return (err == hipSuccess) ? n : -1;
+}
+// d_res[0] on the host, as a double (exact for either dtype); false on a HIP error
+static bool read_residual(const drs_kernel *k, const void *d_res, double *r) {
+    if (k->fp32) { float v = 0.f; if (hipMemcpy(&v, d_res, sizeof v, hipMemcpyDeviceToHost) != hipSuccess) return false; *r = (double)v; }
+    else if (hipMemcpy(r, d_res, sizeof *r, hipMemcpyDeviceToHost) != hipSuccess) return false;
+    return true;
+}
+int drs_kernel_residual(const drs_kernel *k, const void *d_res, double *r) {
+    if (!k->launch_res || !d_res || !r) return -2;
+    return read_residual(k, d_res, r) ? 0 : -1;
+}
+int drs_kernel_solve(drs_kernel *k, void *d_a, void *d_b, const void *d_src, void *d_res, double tol, int max_launches, int check_every_pairs, void *stream,
+                     int *launches, double *residual) {
+    if (launches) *launches = 0;
+    if (residual) *residual = std::nan("");
+    if (!res_args_ok(k, d_src, d_res) || check_every_pairs < 1) return -2;
+    const int limit = max_launches < 0 ? 0 : max_launches - max_launches % 2;
+    int n = 0;
+    double r = std::nan("");
+    g_launched = true;
+    while (n < limit) {
+        const int pairs = std::min(check_every_pairs, (limit - n) / 2);
+        for (int i = 0; i < pairs; i++) {
+            if (k->launch_res(d_a, d_b, d_src, d_res, (hipStream_t)stream) != 0) return -1;
+            if (k->launch_res(d_b, d_a, d_src, d_res, (hipStream_t)stream) != 0) return -1;
+        }
+        n += 2 * pairs;
+        if (hipStreamSynchronize((hipStream_t)stream) != hipSuccess || !read_residual(k, d_res, &r)) return -1;
+        if (launches) *launches = n;
+        if (residual) *residual = r;
+        if (std::isnan(r) || std::isinf(r)) return -4;       // diverged or overflowed: reported, not iterated on
+        if (r <= tol) return 0;
+    }
+    return 1;
 }
 
 // ---- inputs and error metric (common.hpp:9-102) -----------------------------------------------

@@ -164,6 +164,7 @@ inline std::string info_json(const Schedule &s) {
                          (o.debug_drop_barrier || o.debug_skip) ? 0 : 1 /* 0: a timing experiment with barriers removed -- its results are wrong by design */);
     if (p.second_order) j.insert(j.size() - 1, ",\\\"time_order\\\":2");
     if (p.source) j.insert(j.size() - 1, ",\\\"source\\\":1");
+    if (p.residual) j.insert(j.size() - 1, sfmt(",\\\"residual\\\":\\\"max\\\",\\\"residual_elems\\\":%ld", s.residual_elems()));
     if (p.periodic) {
         const int H = p.halo;
         j.insert(j.size() - 1, p.ndim == 3 ? sfmt(",\\\"boundary\\\":\\\"periodic\\\",\\\"period\\\":[%d,%d,%d]", p.L - 2 * H, p.M - 2 * H, p.N - 2 * H)
@@ -190,9 +191,19 @@ inline std::string plugin_api(const Schedule &s) {
     const std::string wrap_in = p.fills_ring() ? "    if (int rc = drs_plugin_wrap((void*)in, stream)) return rc;\n" : "";
     // --source kernels take three arrays: they export the _src entry points INSTEAD of the two-pointer ones
     const std::string sfx = p.source ? "_src" : "", src_par = p.source ? ", const void* src" : "", src_arg = p.source ? ", (const real_t*)src" : "";
+    if (p.residual) {
+        // --residual kernels export ONE sweep entry point, with every array in its signature (src is null unless --source), INSTEAD of the others:
+        // the sweep, which writes the DRS_GRID partials d_res[1 ..], then res_<name>, which folds them into d_res[0], on the same stream
+        a << "extern \"C\" int drs_plugin_launch_res(const void* in, void* out, const void* src, void* res, hipStream_t stream)\n{\n" << wrap_in;
+        if (!p.source) a << "    (void)src;\n";
+        a << "    hipLaunchKernelGGL(dr_" << p.name << ", dim3(DRS_GRID), dim3(DRS_NTL), 0, stream, (const real_t*)in, (real_t*)out" << src_arg << ", (real_t*)res);\n";
+        a << "    hipLaunchKernelGGL(res_" << p.name << ", dim3(1), dim3(256), 0, stream, (real_t*)res);\n";
+        a << "    return (int)hipGetLastError();\n}\n";
+    } else {
     a << "extern \"C\" int drs_plugin_launch" << sfx << "(const void* in, void* out" << src_par << ", hipStream_t stream)\n{\n" << wrap_in;
     a << "    hipLaunchKernelGGL(dr_" << p.name << ", dim3(DRS_GRID), dim3(DRS_NTL), 0, stream, (const real_t*)in, (real_t*)out" << src_arg << ");\n";
     a << "    return (int)hipGetLastError();\n}\n";
+    }
     if (o.pair_launch) {
         a << "extern \"C\" int drs_plugin_launch_pair(const void* in0, void* out0, const void* in1, void* out1, hipStream_t stream)\n{\n";
         a << "    hipLaunchKernelGGL(dr2_" << p.name << ", dim3(DRS_GRID, 2), dim3(DRS_NTL), 0, stream, (const real_t*)in0, (real_t*)out0, (const real_t*)in1, (real_t*)out1);\n";
@@ -594,8 +605,9 @@ inline std::string host_main(const Schedule &s) {
     if (p.second_order) h << "    real_t* h_in = getRandomArray<real_t> (npoints);\n    real_t* h_out = getRandomArray<real_t> (npoints);   // time order 2: out holds u(t-1), input too (the rand() sequence continued)\n";
     else h << "    real_t* h_in = getRandomArray<real_t> (npoints);\n    real_t* h_out = getZeroArray<real_t> (npoints);\n";
     // --source: the third array continues the reference's rand() fill behind the arrays filled today; it lies behind the pair in the same arena
-    const std::string launch = p.source ? "drs_plugin_launch_src" : "drs_plugin_launch", gold = p.source ? "drs_plugin_launch_gold_src" : "drs_plugin_launch_gold";
-    const std::string sarg = p.source ? ", src" : "";
+    const std::string launch = p.residual ? "drs_plugin_launch_res" : p.source ? "drs_plugin_launch_src" : "drs_plugin_launch", gold = p.source ? "drs_plugin_launch_gold_src" : "drs_plugin_launch_gold";
+    const std::string gsarg = p.source ? ", src" : "";                                              // the gold kernel computes no residual
+    const std::string sarg = p.residual ? (p.source ? ", src, d_res" : ", NULL, d_res") : gsarg;
     if (p.source) h << "    real_t* h_src = getRandomArray<real_t> (npoints);   // the source term (the rand() sequence continued)\n";
     h << "    // both arrays in ONE allocation, the output " << (s.out_skew_bytes() >> 20) << " MiB (mod " << (Schedule::kPlacementPeriod >> 20) << " MiB) behind the input: launch time depends on (out - in) mod 64 MiB (--out-skew)\n";
     h << "    const size_t out_at = (nbytes + " << Schedule::kPlacementPeriod - 1 << "UL) / " << Schedule::kPlacementPeriod << "UL * " << Schedule::kPlacementPeriod << "UL + " << s.out_skew_bytes() << "UL;\n";
@@ -609,6 +621,8 @@ inline std::string host_main(const Schedule &s) {
     h << "    char *arena;\n    (void)hipMalloc (&arena, out_at + nbytes);\n    check_error (\"Failed to allocate device memory for in and out.\\n\");\n"
          "    real_t *in = (real_t*)arena, *out = (real_t*)(arena + out_at);\n"
          "    (void)hipMemcpy (in, h_in, nbytes, hipMemcpyHostToDevice);\n    (void)hipMemcpy (out, h_out, nbytes, hipMemcpyHostToDevice);\n\n";
+    if (p.residual) h << "    real_t *d_res;   // --residual: [0] the last launch's max |out - in|, then one partial per workgroup; written whole by every launch\n"
+                         "    (void)hipMalloc (&d_res, sizeof(real_t) * DRS_RES_ELEMS);\n    check_error (\"Failed to allocate device memory for the residual.\\n\");\n";
     h << "    puts(\"GPU computing ...\");\n\n    // warm up\n    for (int i = 0; i < 10; i ++) " << launch << " (in, out" << sarg << ", 0);\n\n";
     if (p.second_order)
         h << "    // time order 2: a launch reads its output, so the warm-up has advanced the state: both arrays start the timed (and checked) sequence afresh\n"
@@ -623,17 +637,37 @@ inline std::string host_main(const Schedule &s) {
          "            printf(\"[Perf] %.3f GStencil/s, %d launches\\n\", updates / (ms * 1e-3) / 1e9, launches);\n"
          "            printf(\"[Perf] achieved %.1f GB/s = %.1f %% of the MI355X HBM3E roofline (8000 GB/s)\\n\", bytes / (ms * 1e-3) / 1e9, bytes / (ms * 1e-3) / 8e12 * 100.0);\n"
          "        }\n    }\n";
+    if (p.residual)
+        h << "    real_t h_res = (real_t)0;\n    (void)hipMemcpy (&h_res, d_res, sizeof(real_t), hipMemcpyDeviceToHost);\n    check_error (\"Failed to read the residual.\\n\");\n"
+             "    printf(\"residual : %.17g\\n\", (double)h_res);\n";
     if (o.check) {
         h << "\n    // run the gold kernel and check error\n    puts (\"Checking error ...\");\n    real_t *g_in, *g_out;\n"
              "    (void)hipMalloc (&g_in, nbytes);\n    check_error (\"Failed to allocate device memory for g_in.\\n\");\n    (void)hipMemcpy (g_in, h_in, nbytes, hipMemcpyHostToDevice);\n"
              "    (void)hipMalloc (&g_out, nbytes);\n    check_error (\"Failed to allocate device memory for g_out.\\n\");\n    (void)hipMemcpy (g_out, h_out, nbytes, hipMemcpyHostToDevice);\n";
-        h << "    for (int t = 0; t < Iterations; t += " << 2 * p.step << ") {\n        " << gold << " (g_in, g_out" << sarg << ", 0);\n        " << gold << " (g_out, g_in" << sarg << ", 0);\n    }\n";
+        h << "    for (int t = 0; t < Iterations; t += " << 2 * p.step << ") {\n        " << gold << " (g_in, g_out" << gsarg << ", 0);\n        " << gold << " (g_out, g_in" << gsarg << ", 0);\n    }\n";
         h << "    (void)hipDeviceSynchronize();\n    check_error (\"Kernel(gold) error\");\n    real_t* h_g_out = h_in;   // reuse the memory of the input array\n"
              "    (void)hipMemcpy (h_out, in, nbytes, hipMemcpyDeviceToHost);\n    (void)hipMemcpy (h_g_out, g_in, nbytes, hipMemcpyDeviceToHost);\n";
         h << "    double error = " << check_call(p, p.ndim == 3 ? "h_out, h_g_out, Halo, L-Halo" : "h_out, h_g_out, Halo, M-Halo") << ";\n";
-        h << "    printf(\"[Test] RMS Error: %e\\n\", error);\n    (void)hipFree (g_in);\n    (void)hipFree (g_out);\n";
+        h << "    printf(\"[Test] RMS Error: %e\\n\", error);\n";
+        if (p.residual) {
+            // the last launch was (out -> in): its residual is max |in - out| over the interior of the arrays as they stand, which gold's arrays give on the host
+            h << "    if (launches > 0) {\n        real_t* h_g_prev = new real_t[npoints];\n        (void)hipMemcpy (h_g_prev, g_out, nbytes, hipMemcpyDeviceToHost);\n"
+                 "        real_t want = (real_t)0;\n";
+            if (p.ndim == 3) h << "        for (int k = Halo; k < L - Halo; k++)\n";
+            h << "        for (int j = Halo; j < M - Halo; j++)\n            for (int i = Halo; i < N - Halo; i++) {\n"
+                 "                const size_t x = " << (p.ndim == 3 ? "((size_t)k * M + j) * N + i" : "(size_t)j * N + i") << ";\n"
+                 "                const real_t diff = h_g_out[x] - h_g_prev[x];          // one rounded subtraction in the array's type\n"
+                 "                const real_t d = diff < 0 ? -diff : diff;\n"
+                 "                want = (d > want || d != d) ? d : want;\n            }\n"
+                 "        const bool same = (want != want && h_res != h_res) || memcmp (&want, &h_res, sizeof(real_t)) == 0;\n"
+                 "        if (!same) printf(\"Residual values differ : %.17g and %.17g\\n\", (double)want, (double)h_res);\n"
+                 "        printf(\"[Test] Residual Error: %e\\n\", same ? 0.0 : (want != want || h_res != h_res) ? 1.0 / 0.0 : fabs ((double)want - (double)h_res));\n"
+                 "        delete[] h_g_prev;\n    }\n";
+        }
+        h << "    (void)hipFree (g_in);\n    (void)hipFree (g_out);\n";
     }
     if (p.source) h << "\n    delete[] h_src;";
+    if (p.residual) h << "\n    (void)hipFree (d_res);";
     h << "\n    delete[] h_in;\n    delete[] h_out;\n    (void)hipFree (arena);\n    return 0;\n}\n#endif\n";
     return h.str();
 }

@@ -135,6 +135,15 @@ MI355X options:
                         written; it must not overlap out; the same src goes to every launch of the ping-pong loop.  The kernel is
                         dr_<name>(in, out, src) and the plugin exports drs_plugin_launch_src / drs_plugin_launch_gold_src.  Needs
                         --step 1; not with --temporal, --gpus N > 1 or --pair-launch 1.
+--residual <max>        A launch also produces the convergence residual of the sweep it has just made: one scalar of the grid's dtype,
+                        r = max over the interior of |out - in|, where out is the value the launch stores (after - out_old and + src where those
+                        are on) and out - in is one rounded subtraction.  The maximum propagates NaN: r is NaN if any term is.  It is fused
+                        into the sweep: every stored value meets the input's value of its cell in registers, each workgroup writes one partial
+                        and a second, one-workgroup kernel folds them -- no atomics, bit-identical to numpy's max(abs(out - in)) on every
+                        schedule.  The launch takes one more array d_res of residual_elems = 1 + grid elements (kernel info), written whole by
+                        every launch: d_res[0] is r.  The stored arrays are those of the same command without the option.  The plugin exports
+                        drs_plugin_launch_res(in, out, src, res) instead of the sweep's launch entry point.  With a fused --step n the
+                        residual is max |S^n(in) - in|.  Only max; not with --temporal, --gpus N > 1 or --pair-launch 1.
 --xrim <lds|dpp>        x halo inside a wavefront by DPP wave shifts (default) or through LDS.
 --schedule <scatter|reuse|window>  How reuse along the streamed dimension is split between source planes kept on chip and
                         partial sums carried in VGPRs (results never depend on it):
@@ -274,6 +283,7 @@ inline constexpr Opt kOptions[] = {
     {"--boundary-y", &GenOptions::boundary_y, "fixed periodic reflect", NAMES, &GenOptions::boundary_y_set},
     {"--boundary-z", &GenOptions::boundary_z, "fixed periodic reflect", NAMES, &GenOptions::boundary_z_set},
     {"--time-order", &GenOptions::time_order, NAMES}, {"--source", &GenOptions::source, NAMES},
+    {"--residual", &GenOptions::residual, "max", NAMES, &GenOptions::residual_set},
     {"--gpus", &GenOptions::gpus, NAMES | LOCAL}, {"--pair-launch", &GenOptions::pair_launch, NAMES}, {"--temporal", put_temporal, NAMES},
     {"--out-skew", &GenOptions::out_skew, NAMES}, {"--tuned-defaults", &GenOptions::tuned_defaults, NAMES},
     {"--schedule", &GenOptions::schedule, "scatter reuse window", 0, &GenOptions::schedule_set},
@@ -430,6 +440,13 @@ inline GenResult generate(const std::vector<std::string> &args /* argv[1..] */) 
                                : "--source cannot be combined with --pair-launch 1 (the pair kernel serves the slab runtime, which has no source term)";
         return res;
     }
+    if (res.plan.residual && (o.gpus > 1 || o.pair_launch)) {
+        // a slab rank's maximum would still have to be reduced over the ranks, and the slab runtime passes no residual array; the pair kernel serves it
+        res.messages += "Invalid configuration!\n"; res.exit_code = 255;
+        res.error = o.gpus > 1 ? "--residual cannot be combined with --gpus N > 1 (the slab runtime passes no residual array and reduces nothing over the ranks)"
+                               : "--residual cannot be combined with --pair-launch 1 (the pair kernel serves the slab runtime, which has no residual)";
+        return res;
+    }
     const Schedule sched(res.plan, o);
     if (!sched.config_error().empty()) { res.messages += "Invalid configuration!\n"; res.exit_code = 255; res.error = sched.config_error(); return res; }
     if (sched.lds_bytes() > 160 * 1024) {   // gfx950: 160 KiB of LDS per workgroup
@@ -470,6 +487,8 @@ inline GenResult generate(const std::vector<std::string> &args /* argv[1..] */) 
     if (res.plan.source)
         res.notes += std::string("drstencil: note: source term: a launch takes a third array and computes out = ") +
                      (res.plan.second_order ? "(S(in) - out_old) + src" : "S(in) + src") + " on the interior (src is read only, in its interior)\n";
+    if (res.plan.residual)
+        res.notes += "drstencil: note: residual: a launch takes one more array of " + std::to_string(sched.residual_elems()) + " elements and writes r = max |out - in| over the interior to its first element (NaN if any term is NaN)\n";
     if (!res.tuned_from.empty())
         res.notes += "drstencil: note: no geometry option given: the tuner's configuration for this stencil, step, dtype and grid size is used (" +
                      res.tuned_from + "); --tuned-defaults 0 keeps the generic defaults\n";

@@ -185,6 +185,11 @@ struct GenOptions {
                                  // interior (a Jacobi sweep for Poisson's equation, a heat source, a forcing term of the wave equation); with
                                  // --time-order 2, out = (S(in) - out_old) + src.  src is one more memory stream of the sweep, read once.  It names
                                  // the problem, not a tuning choice
+    std::string residual;        // --residual max: a launch also produces r = max over the interior of |out - in|, the convergence residual of the
+                                 // sweep it has just made: every stored value meets the input's value of its own cell in registers (one more read
+                                 // stream, from `in`), each lane keeps a running maximum, each workgroup writes one partial and a second, one-workgroup
+                                 // kernel folds the partials.  No atomics, nothing initialised by the caller.  It names the problem, not a tuning choice
+    bool residual_set = false;
 };
 
 // ---- boundary modes per axis (0 z, 1 y, 2 x; z counts as fixed in 2D)
@@ -257,6 +262,7 @@ struct KernelPlan {
     bool all_axes(int m) const { return (ndim == 2 || bmode[0] == m) && bmode[1] == m && bmode[2] == m; }
     bool second_order = false;   // --time-order 2: out = S(in) - out_old on the interior (out's interior is input, each cell's old value reaching only that cell)
     bool source = false;         // --source: out = S(in) + src (order 2: (S(in) - out_old) + src) on the interior; src's interior is read, each value reaching only its own cell
+    bool residual = false;       // --residual max: the launch also writes r = max |out - in| over the interior (NaN if any term is NaN) to d_res[0]
     std::string error;       // non-empty: invalid configuration
     std::string note;        // non-empty: something the user asked for was not done (printed by the generator, kept in the banner)
 };

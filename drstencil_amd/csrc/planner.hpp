@@ -295,6 +295,9 @@ inline KernelPlan make_plan(const Stencil &st, const GenOptions &o_in, const std
     p.source = o.source;
     if (p.source && o_in.step > 1) { p.error = "--source needs --step 1 (a fused S^n plus the source is not n forced steps)"; return p; }
     if (p.source && o_in.temporal) { p.error = "--source cannot be combined with --temporal (on-chip stages fuse time steps; every forced step adds the source)"; return p; }
+    // --residual max: the residual of a launch is that of its stored values against its input; on-chip stages have no place where both meet
+    p.residual = (o.residual == "max");
+    if (p.residual && o_in.temporal) { p.error = "--residual cannot be combined with --temporal (on-chip stages keep the intermediate steps on the chip: the sweep that stores never holds the input's centre values)"; return p; }
 
     if (o.loader_waves > 0 && o.stage != "dma") { p.error = "--loader-waves goes with --stage dma"; return p; }
     if (o.stage == "dma") {

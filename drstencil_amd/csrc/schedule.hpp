@@ -78,7 +78,7 @@ struct Schedule {
     // 32-bit registers of the per-lane state the kernel names: partial sums, register windows (own points + rims) and the
     // prefetch sets.  The tuner's FilterParams compares it with the register file a lane can have at the workgroup's size
     // (drstencil_amd/tuner/tuning.py: fitted against the compiler's resource reports, profiles/r02_reg_model.md).
-    int reg_demand() const { return reg_demand_sweep() + (p.fp32 ? 1 : 2) * extra_streams() * old_sets() * p.RY * p.VX; }
+    int reg_demand() const { return reg_demand_sweep() + (p.fp32 ? 1 : 2) * (extra_streams() * old_sets() * p.RY * p.VX + residual_words()); }
     // ---- --time-order 2: the old output, the sweep's third memory stream -----------------------------------------------------------
     // out = S(in) - out_old.  The old vector of every (r, q) the lane stores is loaded into named registers ov<set>_<r>_<q>, under the
     // store's own guards, old_dist() planes AHEAD of the iteration that completes and stores that plane: with --prefetch at the prefetch
@@ -87,9 +87,16 @@ struct Schedule {
     // PD + 1).  The value is read once: a non-temporal load.  emit_final subtracts it from the finished sums in place.
     // ---- --source: the source term is one more stream of the same kind, from a third array: out = S(in) + src, or (S(in) - out_old) + src.
     // Both extra read streams share the distance and each has its own family of old_dist() + 1 register sets (sv<set>_<r>_<q> beside ov...).
+    // ---- --residual max: the centre value is a third stream of that kind, from `in` itself: the input's value at every cell the lane stores
+    // (cv<set>_<r>_<q>), same guards, same distance, same number of sets -- but ordinary cached loads (the workgroup fetched these lines a few
+    // planes earlier) and nothing is applied to the sums: emit_final folds |sum - centre| of every stored element into the lane's running
+    // maximum rmax.  At every exit of the kernel the workgroup reduces its lanes' maxima (cross-lane inside a wavefront, one value per
+    // wavefront through the LDS image, which is free by then) and writes ONE partial, d_res[1 + blockIdx.x]; res_<name> folds them.
     int extra_streams() const { return (p.second_order ? 1 : 0) + (p.source ? 1 : 0); }
-    int old_dist() const { return (extra_streams() && p.prefetch && p.has_s && !p.dma) ? PD : 0; }
+    int old_dist() const { return ((extra_streams() || p.residual) && p.prefetch && p.has_s && !p.dma) ? PD : 0; }
     int old_sets() const { return old_dist() + 1; }
+    int residual_words() const { return p.residual ? old_sets() * p.RY * p.VX + 1 : 0; }      // elements: the centre sets and rmax
+    long residual_elems() const { return p.residual ? 1L + grid_size() : 0L; }                // d_res: the result, then one partial per launched workgroup
     int reg_demand_sweep() const {
         const int words = p.fp32 ? 1 : 2, pts = p.RY * p.VX;
         const int stg = (p.prefetch && p.has_s ? PD + 1 : 1) * (pts + hl_iters() * p.VL);   // the staged plane and the prefetch sets
@@ -308,6 +315,7 @@ struct Schedule {
             const int base_un = UN;
             while (UN < o.stream_unroll && UN < 16) UN += base_un;
         }
+        if (p.residual && lds_elems() < ceil_div(p.NT, 64)) cfg_error_ = "--residual: the LDS image holds fewer elements than the workgroup has wavefronts";
         if (o.skew > 0 && p.stages > 1 && !skewed()) cfg_error_ = "--skew 1 needs a streaming temporal pipeline with --prefetch (register staging)";
         if (rows_order()) {
             if (!scatter()) cfg_error_ = "--order rows needs the scatter schedule (every partial sum carried)";

@@ -71,6 +71,12 @@ def refuse_source(opts, who):
         raise ValueError("%s: --source is not supported by the slab decomposition (it passes no view of a source array); run it on one GPU" % who)
 
 
+def refuse_residual(opts, who):
+    """--residual has no slab form: a rank's maximum would have to be reduced over the ranks, and the slab classes pass no residual array."""
+    if "--residual" in list(opts or ()):
+        raise ValueError("%s: --residual is not supported by the slab decomposition (it passes no residual array and reduces nothing over the ranks); run it on one GPU" % who)
+
+
 def slab_bounds(L, world, rank):
     """Planes [z0, z1) owned by `rank` (balanced split of the outermost dim)."""
     return (rank * L) // world, ((rank + 1) * L) // world
@@ -316,8 +322,10 @@ class HipSweep:
         refuse_periodic(alone_opts, "HipSweep")
         refuse_second_order(opts, "HipSweep")
         refuse_source(opts, "HipSweep")
+        refuse_residual(opts, "HipSweep")
         refuse_second_order(alone_opts, "HipSweep")
         refuse_source(alone_opts, "HipSweep")
+        refuse_residual(alone_opts, "HipSweep")
         self.base_stc, self.opts, self.cache_dir = base_stc, list(opts), cache_dir
         self.alone_opts = list(alone_opts) if alone_opts else None
         self.ndim = 3 if "--3d" in self.opts else 2
@@ -433,6 +441,7 @@ class SlabRun:
         refuse_periodic(getattr(sweep, "opts", None), "SlabRun")
         refuse_second_order(getattr(sweep, "opts", None), "SlabRun")
         refuse_source(getattr(sweep, "opts", None), "SlabRun")
+        refuse_residual(getattr(sweep, "opts", None), "SlabRun")
         self.torch, self.dist = torch, dist
         dims = tuple(dims)
         self.plan = SlabPlan(dims[0], H, world, rank, every if world > 1 else 1)
@@ -625,8 +634,10 @@ class NativeSlabRun:
         refuse_periodic(alone_opts, "NativeSlabRun")
         refuse_second_order(opts, "NativeSlabRun")
         refuse_source(opts, "NativeSlabRun")
+        refuse_residual(opts, "NativeSlabRun")
         refuse_second_order(alone_opts, "NativeSlabRun")
         refuse_source(alone_opts, "NativeSlabRun")
+        refuse_residual(alone_opts, "NativeSlabRun")
         self.torch, self.dist = torch, dist
         dims = tuple(dims)
         pworld = rehearse_world or world

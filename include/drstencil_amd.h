@@ -69,7 +69,8 @@ int drs_kernel_unload(drs_kernel *k);
  *                                  different modes (--boundary reflect, --boundary-z / -y / -x): "fixed" | "periodic" | "reflect" per
  *                                  axis, three entries in 3D, two in 2D.  Neither key: every axis is fixed.
  *   "time_order": 2                only for kernels generated with --time-order 2 (see drs_kernel_launch).
- *   "source": 1                    only for kernels generated with --source (see drs_kernel_launch_src). */
+ *   "source": 1                    only for kernels generated with --source (see drs_kernel_launch_src).
+ *   "residual": "max", "residual_elems": N   only for kernels generated with --residual max (see drs_kernel_launch_res): N = 1 + "grid". */
 const char *drs_kernel_info(const drs_kernel *k);
 const char *drs_kernel_path(const drs_kernel *k);   /* the loaded shared object */
 /* JSON: vgprs, agprs, sgprs, scratch_bytes_per_lane, sgpr_spill, vgpr_spill, occupancy_waves_per_simd, lds_bytes of
@@ -138,6 +139,43 @@ int drs_kernel_launch_src(drs_kernel *k, const void *d_in, void *d_out, const vo
 int drs_kernel_launch_gold_src(drs_kernel *k, const void *d_in, void *d_out, const void *d_src, void *stream);
 int drs_kernel_run_src(drs_kernel *k, void *d_a, void *d_b, const void *d_src, int iterations, int gold, void *stream);
 int drs_kernel_run_timed_src(drs_kernel *k, void *d_a, void *d_b, const void *d_src, int iterations, int warmup, void *stream, float *ms);
+
+/* ---- --residual max kernels: the convergence residual of every launch, fused into the sweep ----------------------------------------------
+ * No reference counterpart.  A kernel generated with --residual max is dr_<name>(in, out[, src], res): beside the sweep it writes
+ *     d_res[0] = max over the interior of |d_out - d_in|
+ * in the grid's dtype, d_out being the value the launch stores (after - out_old and + src where those options are on), the difference one
+ * rounded subtraction, |.| clearing the sign, and the maximum PROPAGATING NaN (NaN if any term is NaN, else the largest term, +0.0 for an
+ * all-zero difference): bit for bit numpy's max(abs(out[I] - in[I])).  With a fused --step n it is max |S^n(in) - in|.  The stored arrays
+ * are those of the same command without the option.
+ * d_res holds drs_kernel_residual_elems(k) = 1 + grid elements of the grid's dtype (0 for a kernel without the option; "residual_elems" of
+ * the kernel info): [0] the result, then one partial per launched workgroup.  Every launch WRITES ALL OF THEM and reads only what it has
+ * written itself: the caller initialises nothing and nothing carries over between launches.  d_res is element aligned and must not overlap the
+ * other arrays.  A launch also reads d_in at every interior cell (new only for stencils without a centre tap); it touches nothing outside
+ * the arrays.  The launch enqueues two kernels on `stream`: the sweep, then res_<name>, one workgroup that folds the partials.
+ * The plugin exports drs_plugin_launch_res INSTEAD of the sweep's launch entry point: drs_kernel_launch, _launch_src, _run, _run_src,
+ * _run_timed and _run_timed_src return -2 on such a kernel, and the entry points below return -2 on a kernel generated without
+ * --residual, on a null d_res, and when d_src does not go with the kernel (null on a --source kernel, non-null on one without).
+ * gold_<name> computes no residual and keeps its entry points (drs_kernel_launch_gold / _launch_gold_src): a reference takes the
+ * residual from gold's arrays on the host.  -1 is a HIP error.  --temporal, --gpus N > 1, --pair-launch 1 and the drs_slab_* runtime
+ * refuse --residual. */
+long drs_kernel_residual_elems(const drs_kernel *k);
+/* one launch (in -> out) and its residual into d_res[0]; asynchronous on `stream` */
+int drs_kernel_launch_res(drs_kernel *k, const void *d_in, void *d_out, const void *d_src, void *d_res, void *stream);
+/* the reference's loop, for (t = 0; t < iterations; t += 2*step) { k(A,B); k(B,A); }: the number of launches; d_res[0] then holds the LAST
+ * launch's residual.  Asynchronous on `stream`. */
+int drs_kernel_run_res(drs_kernel *k, void *d_a, void *d_b, const void *d_src, void *d_res, int iterations, void *stream);
+/* drs_kernel_run_timed with the residual array: `warmup` launches (A,B), then the loop above between two events; blocks until done */
+int drs_kernel_run_timed_res(drs_kernel *k, void *d_a, void *d_b, const void *d_src, void *d_res, int iterations, int warmup, void *stream, float *ms);
+/* d_res[0] of a --residual kernel copied to the host as a double (exact for either dtype); the copy synchronises with the device */
+int drs_kernel_residual(const drs_kernel *k, const void *d_res, double *r);
+/* Run to tolerance.  Repeats: enqueue `check_every_pairs` (>= 1) ping-pong pairs k(A,B); k(B,A) -- fewer when `max_launches`, rounded down
+ * to an even number, would be passed --, synchronise `stream`, copy d_res[0] (the last launch's residual r) to the host, decide:
+ *     0   r <= tol
+ *     1   max_launches reached (also when it allows no pair: *launches = 0, *residual = NaN)
+ *    -4   r is NaN or inf: a diverged or overflowed run is reported instead of iterated on
+ * (-2 and -1 as above).  *launches = launches made, *residual = the last r read (either may be NULL).  The answer is always in d_a. */
+int drs_kernel_solve(drs_kernel *k, void *d_a, void *d_b, const void *d_src, void *d_res, double tol, int max_launches, int check_every_pairs, void *stream,
+                     int *launches, double *residual);
 
 /* ---- N > 1: one rank of a slab-decomposed run (z slabs in 3D, y slabs in 2D), one process per GPU -----------------------------
  * No reference counterpart: the reference is single-GPU (no cudaSetDevice / streams / NCCL anywhere; SURVEY.md section 5 sketches

@@ -208,8 +208,29 @@ def source_lists():
     return [(None, l) for l in lists] + [(None, j) for j in source_cases.all_build_args()]       # what build() emits for the source tests
 
 
+def residual_lists():
+    """--residual max.  Behind everything else, so that the lists in front keep their numbers: against a build without the option `diff -r`
+    shows these files (and --help) and nothing else."""
+    import residual_cases
+    res3 = ["--3d", "--dtype", "fp32", "--residual", "max", "--check"]
+    lists = [
+        # the emitted main() with the residual array, every issue point of the centre stream, all three streams at once, the knob bases
+        res3 + [stc("t3_wave")], res3 + ["--store-mask", "buffer", stc("t3_wave")],
+        res3 + ["--prefetch", "--prefetch-depth", "2", stc("t3_wave")], res3 + ["--source", "--time-order", "2", "--prefetch", "--prefetch-depth", "2", stc("t3_wave")],
+        ["--3d", "--dtype", "fp64", "--residual", "max", "--check", "--stage", "dma", "--loader-waves", "1", stc("t3_star")], res3 + ["--step", "2", stc("t3_star")],
+        ["--dtype", "fp64", "--residual", "max", "--check", stc("t2_wave")], ["--dtype", "fp64", "--residual", "max", "--streaming", "--stage", "dma", stc("t2_star")],
+        # rejected before the emitter is asked
+        ["--3d", "--residual", "l2", stc("t3_star")], ["--3d", "--residual", "max", "--step", "2", "--temporal", "1", stc("t3_star")],
+        ["--3d", "--residual", "max", "--gpus", "2", stc("t3_star")], ["--3d", "--residual", "max", "--pair-launch", "1", stc("t3_star")],
+    ]
+    for b in ("d3", "d3f64", "rows", "tile", "cross", "stream", "odd"):
+        opts, name = BASES[b]
+        lists.append(list(opts) + ["--residual", "max", stc(name)])
+    return [(None, l) for l in lists] + [(None, j) for j in residual_cases.all_build_args()]       # what build() emits for the residual tests
+
+
 def corpus():
-    return build_lists() + space_sample() + host_lists() + knob_lists() + boundary_lists() + source_lists()
+    return build_lists() + space_sample() + host_lists() + knob_lists() + boundary_lists() + source_lists() + residual_lists()
 
 
 def coverage(lists):
