@@ -73,6 +73,11 @@ def lib():
     L.drs_kernel_launch_res.argtypes = [vp, vp, vp, vp, vp, vp]
     L.drs_kernel_run_res.argtypes = [vp, vp, vp, vp, vp, ci, vp]
     L.drs_kernel_run_timed_res.argtypes = [vp, vp, vp, vp, vp, ci, ci, vp, ctypes.POINTER(ctypes.c_float)]
+    L.drs_kernel_launch_fix.argtypes = [vp, vp, vp, vp, vp, vp, vp]
+    L.drs_kernel_launch_gold_fix.argtypes = [vp, vp, vp, vp, vp, vp]
+    L.drs_kernel_run_fix.argtypes = [vp, vp, vp, vp, vp, vp, ci, ci, vp]
+    L.drs_kernel_run_timed_fix.argtypes = [vp, vp, vp, vp, vp, vp, ci, ci, vp, ctypes.POINTER(ctypes.c_float)]
+    L.drs_kernel_solve_fix.argtypes = [vp, vp, vp, vp, vp, vp, ctypes.c_double, ci, ci, vp, ctypes.POINTER(ci), ctypes.POINTER(ctypes.c_double)]
     L.drs_kernel_residual.argtypes = [vp, vp, ctypes.POINTER(ctypes.c_double)]
     L.drs_kernel_solve.argtypes = [vp, vp, vp, vp, vp, ctypes.c_double, ci, ci, vp, ctypes.POINTER(ci), ctypes.POINTER(ctypes.c_double)]
     L.drs_slab_unique_id.argtypes = [vp]
@@ -107,6 +112,7 @@ EXPORTS = [
     "drs_kernel_wrap", "drs_kernel_launch_gold", "drs_kernel_run", "drs_kernel_run_timed",
     "drs_kernel_launch_src", "drs_kernel_launch_gold_src", "drs_kernel_run_src", "drs_kernel_run_timed_src",
     "drs_kernel_residual_elems", "drs_kernel_launch_res", "drs_kernel_run_res", "drs_kernel_run_timed_res", "drs_kernel_residual", "drs_kernel_solve",
+    "drs_kernel_launch_fix", "drs_kernel_launch_gold_fix", "drs_kernel_run_fix", "drs_kernel_run_timed_fix", "drs_kernel_solve_fix",
     "drs_fill_random_f64", "drs_fill_random_f32", "drs_check_error_f64", "drs_check_error_f32",
     "drs_slab_unique_id", "drs_slab_open", "drs_slab_plan", "drs_slab_connect", "drs_slab_run", "drs_slab_sync", "drs_slab_stream", "drs_slab_info",
     "drs_slab_error", "drs_slab_close",
@@ -238,6 +244,21 @@ class Kernel:
             raise ValueError("%s(): d_res given, but the kernel was generated without --residual" % who)
         return d_res
 
+    def _fix(self, d_fix, who):
+        """The array of held cells of a call, checked against the kernel: a --dirichlet kernel needs one, any other kernel takes none."""
+        if self.dirichlet and not d_fix:
+            raise ValueError("%s(): the kernel was generated with --dirichlet and needs d_fix, the array of held cells" % who)
+        if not self.dirichlet and d_fix is not None:
+            raise ValueError("%s(): d_fix given, but the kernel was generated without --dirichlet" % who)
+        return d_fix
+
+    @property
+    def dirichlet(self):
+        """True for kernels generated with --dirichlet: a launch takes one more read-only array d_fix of the grid's shape and dtype and
+        stores out = fix wherever fix is not NaN (a held cell, bit for bit), else the value the kernel would store without the option (a free
+        cell).  launch, launch_gold, run, run_timed and solve then need the keyword d_fix, the same array for every launch of a loop."""
+        return bool(self.info.get("dirichlet", 0))
+
     @property
     def residual_elems(self):
         """Elements of the residual array of a kernel generated with --residual max (1 + launched workgroups, of the grid's dtype; every
@@ -254,21 +275,26 @@ class Kernel:
             raise RuntimeError("HIP error reading the residual")
         return float(v.value)
 
-    def solve(self, d_a, d_b, d_res, tol, max_launches, check_every=8, d_src=None, stream=0):
+    def solve(self, d_a, d_b, d_res, tol, max_launches, check_every=8, d_src=None, stream=0, d_fix=None):
         """Run to tolerance (drs_kernel_solve): ping-pong pairs k(A,B); k(B,A), `check_every` pairs between two looks at the residual, until
         it is <= tol.  (status, launches, residual): status 0 converged, 1 max_launches (rounded down to an even number) reached, -4 the
-        residual is NaN or inf (a diverged or overflowed run).  The answer is in A."""
+        residual is NaN or inf (a diverged or overflowed run).  The answer is in A.  --dirichlet kernels: d_fix, the held cells (drs_kernel_solve_fix)."""
         self._res(d_res, "solve")
         n, r = ctypes.c_int(), ctypes.c_double()
-        rc = lib().drs_kernel_solve(self.h, d_a, d_b, self._src(d_src, "solve"), d_res, tol, max_launches, check_every, stream, ctypes.byref(n), ctypes.byref(r))
+        if self._fix(d_fix, "solve"):
+            rc = lib().drs_kernel_solve_fix(self.h, d_a, d_b, self._src(d_src, "solve"), d_res, d_fix, tol, max_launches, check_every, stream, ctypes.byref(n), ctypes.byref(r))
+        else:
+            rc = lib().drs_kernel_solve(self.h, d_a, d_b, self._src(d_src, "solve"), d_res, tol, max_launches, check_every, stream, ctypes.byref(n), ctypes.byref(r))
         if rc == -2:
             raise ValueError("solve(): the kernel was generated without --residual, or check_every < 1")
         if rc == -1:
             raise RuntimeError("HIP error in drs_kernel_solve")
         return rc, n.value, r.value
 
-    def launch(self, d_in, d_out, stream=0, d_src=None, d_res=None):
-        if self._res(d_res, "launch"):
+    def launch(self, d_in, d_out, stream=0, d_src=None, d_res=None, d_fix=None):
+        if self._fix(d_fix, "launch"):
+            rc = lib().drs_kernel_launch_fix(self.h, d_in, d_out, self._src(d_src, "launch"), self._res(d_res, "launch"), d_fix, stream)
+        elif self._res(d_res, "launch"):
             rc = lib().drs_kernel_launch_res(self.h, d_in, d_out, self._src(d_src, "launch"), d_res, stream)
         elif self._src(d_src, "launch"):
             rc = lib().drs_kernel_launch_src(self.h, d_in, d_out, d_src, stream)
@@ -326,29 +352,34 @@ class Kernel:
         if rc != 0:
             raise RuntimeError("HIP launch error %d" % rc)
 
-    def launch_gold(self, d_in, d_out, stream=0, d_src=None):
-        if self._src(d_src, "launch_gold"):
+    def launch_gold(self, d_in, d_out, stream=0, d_src=None, d_fix=None):
+        if self._fix(d_fix, "launch_gold"):
+            rc = lib().drs_kernel_launch_gold_fix(self.h, d_in, d_out, self._src(d_src, "launch_gold"), d_fix, stream)
+        elif self._src(d_src, "launch_gold"):
             rc = lib().drs_kernel_launch_gold_src(self.h, d_in, d_out, d_src, stream)
         else:
             rc = lib().drs_kernel_launch_gold(self.h, d_in, d_out, stream)
         if rc != 0:
             raise RuntimeError("HIP launch error %d" % rc)
 
-    def run(self, d_a, d_b, iterations=None, gold=False, stream=0, d_src=None, d_res=None):
+    def run(self, d_a, d_b, iterations=None, gold=False, stream=0, d_src=None, d_res=None, d_fix=None):
         """The reference's ping-pong loop (codegen.hpp:581-584); result ends in A.  --source kernels: the same d_src in every launch.
         --residual kernels: d_res[0] then holds the last launch's residual (the gold kernel computes none: gold=True takes no d_res)."""
         it = self.info["iterations"] if iterations is None else iterations
+        self._fix(d_fix, "run")
         if gold and self.residual_elems:
             # gold_<name> keeps its entry point: the loop is made of single launches
             if d_res is not None:
                 raise ValueError("run(): the gold kernel computes no residual")
             n = 0
             for t in range(0, it, 2 * self.info["step"]):
-                self.launch_gold(d_a, d_b, stream, d_src)
-                self.launch_gold(d_b, d_a, stream, d_src)
+                self.launch_gold(d_a, d_b, stream, d_src, d_fix)
+                self.launch_gold(d_b, d_a, stream, d_src, d_fix)
                 n += 2
             return n
-        if self._res(d_res, "run"):
+        if d_fix:
+            n = lib().drs_kernel_run_fix(self.h, d_a, d_b, self._src(d_src, "run"), self._res(d_res, "run"), d_fix, it, 1 if gold else 0, stream)
+        elif self._res(d_res, "run"):
             n = lib().drs_kernel_run_res(self.h, d_a, d_b, self._src(d_src, "run"), d_res, it, stream)
         elif self._src(d_src, "run"):
             n = lib().drs_kernel_run_src(self.h, d_a, d_b, d_src, it, 1 if gold else 0, stream)
@@ -382,11 +413,13 @@ class Kernel:
             out.append(("top", dim0 - nsl))
         return out
 
-    def run_timed(self, d_a, d_b, iterations=None, warmup=10, stream=0, d_src=None, d_res=None):
+    def run_timed(self, d_a, d_b, iterations=None, warmup=10, stream=0, d_src=None, d_res=None, d_fix=None):
         """Warm-up launches + timed loop bracketed by HIP events on `stream`: (launches, ms)."""
         it = self.info["iterations"] if iterations is None else iterations
         ms = ctypes.c_float()
-        if self._res(d_res, "run_timed"):
+        if self._fix(d_fix, "run_timed"):
+            n = lib().drs_kernel_run_timed_fix(self.h, d_a, d_b, self._src(d_src, "run_timed"), self._res(d_res, "run_timed"), d_fix, it, warmup, stream, ctypes.byref(ms))
+        elif self._res(d_res, "run_timed"):
             n = lib().drs_kernel_run_timed_res(self.h, d_a, d_b, self._src(d_src, "run_timed"), d_res, it, warmup, stream, ctypes.byref(ms))
         elif self._src(d_src, "run_timed"):
             n = lib().drs_kernel_run_timed_src(self.h, d_a, d_b, d_src, it, warmup, stream, ctypes.byref(ms))
@@ -417,7 +450,8 @@ class Kernel:
         pts = i["M"] * i["N"] * (i["L"] if i["ndim"] == 3 else 1)
         # --time-order 2 also reads the old output, --source the source array: one more whole array each is the algorithmic minimum (the centre
         # values of --residual are cells the sweep reads anyway)
-        return (2 + (self.time_order == 2) + self.source) * (4 if i["dtype"] == "fp32" else 8) * pts
+        # --dirichlet reads the array of held cells: one more whole array
+        return (2 + (self.time_order == 2) + self.source + self.dirichlet) * (4 if i["dtype"] == "fp32" else 8) * pts
 
     # ---- placement of the output array (csrc/schedule.hpp: Schedule::out_skew_bytes; profiles/r03_probe_skew4.log) ----
     def array_bytes(self):

@@ -39,6 +39,9 @@ struct drs_kernel {
     int (*launch_gold_src)(const void *, void *, const void *, hipStream_t) = nullptr;
     // --residual kernels: ONE sweep entry point with every array in its signature (src null unless --source), INSTEAD of launch / launch_src
     int (*launch_res)(const void *, void *, const void *, void *, hipStream_t) = nullptr;
+    // --dirichlet kernels: these two, with every array in their signatures (src / res null unless --source / --residual), INSTEAD of all the others
+    int (*launch_fix)(const void *, void *, const void *, void *, const void *, hipStream_t) = nullptr;
+    int (*launch_gold_fix)(const void *, void *, const void *, const void *, hipStream_t) = nullptr;
     long residual_elems = 0;     // elements of d_res (1 + launched workgroups); 0: no --residual
     bool has_source = false, fp32 = false;
     int (*wrap)(void *, hipStream_t) = nullptr;              // only with a non-fixed boundary (--boundary periodic / reflect, --boundary-x / -y / -z)
@@ -349,6 +352,8 @@ drs_kernel *drs_kernel_build(int argc, const char *const *argv, const char *cach
     k->launch_src = (int (*)(const void *, void *, const void *, hipStream_t))dlsym(dl, "drs_plugin_launch_src");
     k->launch_gold_src = (int (*)(const void *, void *, const void *, hipStream_t))dlsym(dl, "drs_plugin_launch_gold_src");
     k->launch_res = (int (*)(const void *, void *, const void *, void *, hipStream_t))dlsym(dl, "drs_plugin_launch_res");
+    k->launch_fix = (int (*)(const void *, void *, const void *, void *, const void *, hipStream_t))dlsym(dl, "drs_plugin_launch_fix");
+    k->launch_gold_fix = (int (*)(const void *, void *, const void *, const void *, hipStream_t))dlsym(dl, "drs_plugin_launch_gold_fix");
     k->has_source = r.plan.source;
     k->fp32 = r.plan.fp32;
     k->residual_elems = r.plan.residual ? Schedule(r.plan, r.opt).residual_elems() : 0;
@@ -366,7 +371,11 @@ drs_kernel *drs_kernel_build(int argc, const char *const *argv, const char *cach
     const bool sweep_src = with_res ? sweep_plain : (k->launch_src && !k->launch && !k->launch_res);
     const bool plain = sweep_plain && k->launch_gold && !k->launch_gold_src;
     const bool with_src = sweep_src && k->launch_gold_src && !k->launch_gold;
-    if (!(plain || with_src) || with_src != r.plan.source || !k->info) {
+    // --dirichlet: its two entry points and none of the others
+    const bool others = k->launch || k->launch_gold || k->launch_src || k->launch_gold_src || k->launch_res;
+    const bool with_fix = k->launch_fix && k->launch_gold_fix && !others;
+    const bool fix_ok = r.plan.dirichlet ? with_fix : (!k->launch_fix && !k->launch_gold_fix);
+    if (!fix_ok || (!r.plan.dirichlet && (!(plain || with_src) || with_src != r.plan.source)) || !k->info) {
         if (log) *log = dup_cstr("plugin " + so + " lacks the drs_plugin_* entry points\n");
         dlclose(dl);
         delete k;
@@ -545,7 +554,7 @@ static bool read_residual(const drs_kernel *k, const void *d_res, double *r) {
     return true;
 }
 int drs_kernel_residual(const drs_kernel *k, const void *d_res, double *r) {
-    if (!k->launch_res || !d_res || !r) return -2;
+    if (!k->residual_elems || !d_res || !r) return -2;
     return read_residual(k, d_res, r) ? 0 : -1;
 }
 int drs_kernel_solve(drs_kernel *k, void *d_a, void *d_b, const void *d_src, void *d_res, double tol, int max_launches, int check_every_pairs, void *stream,
@@ -562,6 +571,83 @@ int drs_kernel_solve(drs_kernel *k, void *d_a, void *d_b, const void *d_src, voi
         for (int i = 0; i < pairs; i++) {
             if (k->launch_res(d_a, d_b, d_src, d_res, (hipStream_t)stream) != 0) return -1;
             if (k->launch_res(d_b, d_a, d_src, d_res, (hipStream_t)stream) != 0) return -1;
+        }
+        n += 2 * pairs;
+        if (hipStreamSynchronize((hipStream_t)stream) != hipSuccess || !read_residual(k, d_res, &r)) return -1;
+        if (launches) *launches = n;
+        if (residual) *residual = r;
+        if (std::isnan(r) || std::isinf(r)) return -4;       // diverged or overflowed: reported, not iterated on
+        if (r <= tol) return 0;
+    }
+    return 1;
+}
+
+// ---- --dirichlet kernels: held cells.  Every array in every signature: d_src / d_res are null exactly when the kernel was generated without
+// --source / --residual max; d_fix is never null -------------------------------------------------------------------------------------------
+static bool fix_args_ok(const drs_kernel *k, const void *d_src, const void *d_res, const void *d_fix) {
+    return k->launch_fix && d_fix && (k->has_source ? d_src != nullptr : d_src == nullptr) && (k->residual_elems ? d_res != nullptr : d_res == nullptr);
+}
+int drs_kernel_launch_fix(drs_kernel *k, const void *d_in, void *d_out, const void *d_src, void *d_res, const void *d_fix, void *stream) {
+    if (!fix_args_ok(k, d_src, d_res, d_fix)) return -2;      // the kernel was not generated with --dirichlet, no fix array, or a src / res array that does not go with the kernel
+    g_launched = true;
+    return k->launch_fix(d_in, d_out, d_src, d_res, d_fix, (hipStream_t)stream);
+}
+int drs_kernel_launch_gold_fix(drs_kernel *k, const void *d_in, void *d_out, const void *d_src, const void *d_fix, void *stream) {
+    if (!k->launch_gold_fix || !d_fix || (k->has_source ? d_src == nullptr : d_src != nullptr)) return -2;
+    g_launched = true;
+    return k->launch_gold_fix(d_in, d_out, d_src, d_fix, (hipStream_t)stream);
+}
+static int run_loop_fix(drs_kernel *k, void *d_a, void *d_b, const void *d_src, void *d_res, const void *d_fix, int iterations, int gold, void *stream) {
+    auto one = [&](const void *in, void *out) {
+        return gold ? k->launch_gold_fix(in, out, d_src, d_fix, (hipStream_t)stream) : k->launch_fix(in, out, d_src, d_res, d_fix, (hipStream_t)stream);
+    };
+    g_launched = true;
+    int n = 0;
+    for (int t = 0; t < iterations; t += 2 * k->step) {      // step is 1: --dirichlet refuses a fused launch
+        if (one(d_a, d_b) != 0) return -1;
+        if (one(d_b, d_a) != 0) return -1;
+        n += 2;
+    }
+    return n;
+}
+int drs_kernel_run_fix(drs_kernel *k, void *d_a, void *d_b, const void *d_src, void *d_res, const void *d_fix, int iterations, int gold, void *stream) {
+    if (!fix_args_ok(k, d_src, d_res, d_fix)) return -2;
+    return run_loop_fix(k, d_a, d_b, d_src, d_res, d_fix, iterations, gold, stream);
+}
+int drs_kernel_run_timed_fix(drs_kernel *k, void *d_a, void *d_b, const void *d_src, void *d_res, const void *d_fix, int iterations, int warmup, void *stream, float *ms) {
+    if (!fix_args_ok(k, d_src, d_res, d_fix)) return -2;
+    hipStream_t s = (hipStream_t)stream;
+    g_launched = true;
+    for (int i = 0; i < warmup; i++)
+        if (k->launch_fix(d_a, d_b, d_src, d_res, d_fix, s) != 0) return -1;
+    hipEvent_t e0, e1;
+    if (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess) return -1;
+    (void)hipEventRecord(e0, s);
+    const int n = run_loop_fix(k, d_a, d_b, d_src, d_res, d_fix, iterations, 0, stream);
+    (void)hipEventRecord(e1, s);
+    hipError_t err = hipEventSynchronize(e1);
+    float t = 0.f;
+    if (err == hipSuccess) err = hipEventElapsedTime(&t, e0, e1);
+    (void)hipEventDestroy(e0);
+    (void)hipEventDestroy(e1);
+    if (ms) *ms = t;
+    return (err == hipSuccess) ? n : -1;
+}
+// drs_kernel_solve with held cells: the same loop, the same answers; needs --residual max as well
+int drs_kernel_solve_fix(drs_kernel *k, void *d_a, void *d_b, const void *d_src, void *d_res, const void *d_fix, double tol, int max_launches, int check_every_pairs,
+                         void *stream, int *launches, double *residual) {
+    if (launches) *launches = 0;
+    if (residual) *residual = std::nan("");
+    if (!fix_args_ok(k, d_src, d_res, d_fix) || !k->residual_elems || check_every_pairs < 1) return -2;
+    const int limit = max_launches < 0 ? 0 : max_launches - max_launches % 2;
+    int n = 0;
+    double r = std::nan("");
+    g_launched = true;
+    while (n < limit) {
+        const int pairs = std::min(check_every_pairs, (limit - n) / 2);
+        for (int i = 0; i < pairs; i++) {
+            if (k->launch_fix(d_a, d_b, d_src, d_res, d_fix, (hipStream_t)stream) != 0) return -1;
+            if (k->launch_fix(d_b, d_a, d_src, d_res, d_fix, (hipStream_t)stream) != 0) return -1;
         }
         n += 2 * pairs;
         if (hipStreamSynchronize((hipStream_t)stream) != hipSuccess || !read_residual(k, d_res, &r)) return -1;

@@ -144,6 +144,16 @@ MI355X options:
                         every launch: d_res[0] is r.  The stored arrays are those of the same command without the option.  The plugin exports
                         drs_plugin_launch_res(in, out, src, res) instead of the sweep's launch entry point.  With a fused --step n the
                         residual is max |S^n(in) - in|.  Only max; not with --temporal, --gpus N > 1 or --pair-launch 1.
+--dirichlet             Held cells inside the domain: a launch takes one more array fix of the grid's shape and dtype and stores, at every
+                        interior point p, out[p] = (fix[p] != fix[p]) ? v : fix[p], where v is the value the same command without the option
+                        would store (S(in), then - out_old with --time-order 2, then + src with --source).  A cell whose fix is NaN (any sign,
+                        any payload) is free; every other cell is held and receives fix[p] bit for bit (+-0, subnormals and +-inf included).
+                        A select, never arithmetic: a held cell stores fix[p] whatever v is.  S(in) reads in as it is, so write fix into the
+                        input first (and into the output with --time-order 2) if the first launch is to see the held values.  fix is read
+                        in the interior only and never written; it must not overlap out; the same fix goes to every launch.  --residual max
+                        sees the selected value.  The kernel is dr_<name>(in, out, [src,] [res,] fix) and the plugin exports
+                        drs_plugin_launch_fix / drs_plugin_launch_gold_fix instead of the other launch entry points.  Needs --step 1; not with
+                        --temporal, --gpus N > 1 or --pair-launch 1.
 --xrim <lds|dpp>        x halo inside a wavefront by DPP wave shifts (default) or through LDS.
 --schedule <scatter|reuse|window>  How reuse along the streamed dimension is split between source planes kept on chip and
                         partial sums carried in VGPRs (results never depend on it):
@@ -283,7 +293,7 @@ inline constexpr Opt kOptions[] = {
     {"--boundary-y", &GenOptions::boundary_y, "fixed periodic reflect", NAMES, &GenOptions::boundary_y_set},
     {"--boundary-z", &GenOptions::boundary_z, "fixed periodic reflect", NAMES, &GenOptions::boundary_z_set},
     {"--time-order", &GenOptions::time_order, NAMES}, {"--source", &GenOptions::source, NAMES},
-    {"--residual", &GenOptions::residual, "max", NAMES, &GenOptions::residual_set},
+    {"--residual", &GenOptions::residual, "max", NAMES, &GenOptions::residual_set}, {"--dirichlet", &GenOptions::dirichlet, NAMES},
     {"--gpus", &GenOptions::gpus, NAMES | LOCAL}, {"--pair-launch", &GenOptions::pair_launch, NAMES}, {"--temporal", put_temporal, NAMES},
     {"--out-skew", &GenOptions::out_skew, NAMES}, {"--tuned-defaults", &GenOptions::tuned_defaults, NAMES},
     {"--schedule", &GenOptions::schedule, "scatter reuse window", 0, &GenOptions::schedule_set},
@@ -349,6 +359,7 @@ inline bool scan_options(const std::vector<std::string> &args, GenResult &res, s
             continue;
         }
         if (a == "--time-order" && o.time_order == 1) continue;       // likewise
+        if (a == "--dirichlet") continue;                             // echoed once, behind every other option (below)
         echo(a, !(r->attr & LOCAL));
         if (!flag) echo(v, !(r->attr & LOCAL));
     }
@@ -364,6 +375,7 @@ inline bool scan_options(const std::vector<std::string> &args, GenResult &res, s
         long at = first_boundary;
         for (auto &w : boundary_words(o.is3d ? 3 : 2, m)) words.insert(words.begin() + at++, {w, true, true});
     }
+    if (o.dirichlet) words.push_back({"--dirichlet", true, false});     // its canonical place: wherever and however often it stood, the same command
     for (auto &e : words) { banner += (banner.empty() ? "" : " ") + e.w; if (e.slab) o.slab_args.push_back(e.w); }
     return true;
 }
@@ -447,6 +459,13 @@ inline GenResult generate(const std::vector<std::string> &args /* argv[1..] */) 
                                : "--residual cannot be combined with --pair-launch 1 (the pair kernel serves the slab runtime, which has no residual)";
         return res;
     }
+    if (res.plan.dirichlet && (o.gpus > 1 || o.pair_launch)) {
+        // the slab views are windows of two arrays; a view of the array of held cells is no part of the slab runtime, and the pair kernel serves it
+        res.messages += "Invalid configuration!\n"; res.exit_code = 255;
+        res.error = o.gpus > 1 ? "--dirichlet cannot be combined with --gpus N > 1 (the slab runtime passes no view of an array of held cells)"
+                               : "--dirichlet cannot be combined with --pair-launch 1 (the pair kernel serves the slab runtime, which has no held cells)";
+        return res;
+    }
     const Schedule sched(res.plan, o);
     if (!sched.config_error().empty()) { res.messages += "Invalid configuration!\n"; res.exit_code = 255; res.error = sched.config_error(); return res; }
     if (sched.lds_bytes() > 160 * 1024) {   // gfx950: 160 KiB of LDS per workgroup
@@ -489,6 +508,8 @@ inline GenResult generate(const std::vector<std::string> &args /* argv[1..] */) 
                      (res.plan.second_order ? "(S(in) - out_old) + src" : "S(in) + src") + " on the interior (src is read only, in its interior)\n";
     if (res.plan.residual)
         res.notes += "drstencil: note: residual: a launch takes one more array of " + std::to_string(sched.residual_elems()) + " elements and writes r = max |out - in| over the interior to its first element (NaN if any term is NaN)\n";
+    if (res.plan.dirichlet)
+        res.notes += "drstencil: note: held cells: a launch takes one more array fix and stores fix[p] wherever it is not NaN, else the computed value (fix is read only, in its interior)\n";
     if (!res.tuned_from.empty())
         res.notes += "drstencil: note: no geometry option given: the tuner's configuration for this stencil, step, dtype and grid size is used (" +
                      res.tuned_from + "); --tuned-defaults 0 keeps the generic defaults\n";

@@ -190,6 +190,10 @@ struct GenOptions {
                                  // stream, from `in`), each lane keeps a running maximum, each workgroup writes one partial and a second, one-workgroup
                                  // kernel folds the partials.  No atomics, nothing initialised by the caller.  It names the problem, not a tuning choice
     bool residual_set = false;
+    bool dirichlet = false;      // --dirichlet: a launch takes one more read-only array fix of the grid's shape and dtype and stores
+                                 // out[p] = (fix[p] != fix[p]) ? v : fix[p], v the value the same command without the option would store: a cell
+                                 // whose fix is NaN is free, every other cell is held at fix[p], bit for bit.  A select, never arithmetic.  fix is
+                                 // one more memory stream of the sweep, read once.  It names the problem, not a tuning choice
 };
 
 // ---- boundary modes per axis (0 z, 1 y, 2 x; z counts as fixed in 2D)
@@ -263,6 +267,7 @@ struct KernelPlan {
     bool second_order = false;   // --time-order 2: out = S(in) - out_old on the interior (out's interior is input, each cell's old value reaching only that cell)
     bool source = false;         // --source: out = S(in) + src (order 2: (S(in) - out_old) + src) on the interior; src's interior is read, each value reaching only its own cell
     bool residual = false;       // --residual max: the launch also writes r = max |out - in| over the interior (NaN if any term is NaN) to d_res[0]
+    bool dirichlet = false;      // --dirichlet: out = fix where fix is not NaN (held cells), else the value computed as without the option; fix's interior is read, each value reaching only its own cell
     std::string error;       // non-empty: invalid configuration
     std::string note;        // non-empty: something the user asked for was not done (printed by the generator, kept in the banner)
 };

@@ -297,6 +297,11 @@ inline KernelPlan make_plan(const Stencil &st, const GenOptions &o_in, const std
     if (p.source && o_in.temporal) { p.error = "--source cannot be combined with --temporal (on-chip stages fuse time steps; every forced step adds the source)"; return p; }
     // --residual max: the residual of a launch is that of its stored values against its input; on-chip stages have no place where both meet
     p.residual = (o.residual == "max");
+    // --dirichlet: one launch is one step with its held cells re-imposed.  S^n(in) with the result overwritten at the held cells is not n
+    // held steps (the n - 1 intermediate states would have to be held too), fused or staged
+    p.dirichlet = o.dirichlet;
+    if (p.dirichlet && o_in.step > 1) { p.error = "--dirichlet needs --step 1 (a fused S^n through held cells is not n held steps)"; return p; }
+    if (p.dirichlet && o_in.temporal) { p.error = "--dirichlet cannot be combined with --temporal (on-chip stages fuse time steps; every held step re-imposes the held cells)"; return p; }
     if (p.residual && o_in.temporal) { p.error = "--residual cannot be combined with --temporal (on-chip stages keep the intermediate steps on the chip: the sweep that stores never holds the input's centre values)"; return p; }
 
     if (o.loader_waves > 0 && o.stage != "dma") { p.error = "--loader-waves goes with --stage dma"; return p; }

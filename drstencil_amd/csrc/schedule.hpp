@@ -92,7 +92,9 @@ struct Schedule {
     // planes earlier) and nothing is applied to the sums: emit_final folds |sum - centre| of every stored element into the lane's running
     // maximum rmax.  At every exit of the kernel the workgroup reduces its lanes' maxima (cross-lane inside a wavefront, one value per
     // wavefront through the LDS image, which is free by then) and writes ONE partial, d_res[1 + blockIdx.x]; res_<name> folds them.
-    int extra_streams() const { return (p.second_order ? 1 : 0) + (p.source ? 1 : 0); }
+    // ---- --dirichlet: fix is a fourth stream of that kind, from its own array: out = fix where fix is not NaN.  It joins the count: the
+    // same distance, its own family of register sets (fv<set>_<r>_<q>), and emit_final selects with it after the other two are applied.
+    int extra_streams() const { return (p.second_order ? 1 : 0) + (p.source ? 1 : 0) + (p.dirichlet ? 1 : 0); }
     int old_dist() const { return ((extra_streams() || p.residual) && p.prefetch && p.has_s && !p.dma) ? PD : 0; }
     int old_sets() const { return old_dist() + 1; }
     int residual_words() const { return p.residual ? old_sets() * p.RY * p.VX + 1 : 0; }      // elements: the centre sets and rmax

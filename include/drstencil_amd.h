@@ -70,6 +70,7 @@ int drs_kernel_unload(drs_kernel *k);
  *                                  axis, three entries in 3D, two in 2D.  Neither key: every axis is fixed.
  *   "time_order": 2                only for kernels generated with --time-order 2 (see drs_kernel_launch).
  *   "source": 1                    only for kernels generated with --source (see drs_kernel_launch_src).
+ *   "dirichlet": 1                 only for kernels generated with --dirichlet (see drs_kernel_launch_fix).
  *   "residual": "max", "residual_elems": N   only for kernels generated with --residual max (see drs_kernel_launch_res): N = 1 + "grid". */
 const char *drs_kernel_info(const drs_kernel *k);
 const char *drs_kernel_path(const drs_kernel *k);   /* the loaded shared object */
@@ -176,6 +177,36 @@ int drs_kernel_residual(const drs_kernel *k, const void *d_res, double *r);
  * (-2 and -1 as above).  *launches = launches made, *residual = the last r read (either may be NULL).  The answer is always in d_a. */
 int drs_kernel_solve(drs_kernel *k, void *d_a, void *d_b, const void *d_src, void *d_res, double tol, int max_launches, int check_every_pairs, void *stream,
                      int *launches, double *residual);
+
+/* ---- --dirichlet kernels: held cells inside the domain ---------------------------------------------------------------------------------
+ * No reference counterpart.  A kernel generated with --dirichlet is dr_<name>(in, out[, src][, res], fix).  d_fix has the grid's shape
+ * and dtype; at every interior point p the launch stores d_out[p] = (d_fix[p] != d_fix[p]) ? v : d_fix[p], where v is the value the same
+ * command without the option would store (S(in), then - out_old with --time-order 2, then + src with --source).  A cell whose fix is
+ * NaN -- either sign, any payload, signalling ones included -- is FREE; every other cell is HELD and receives d_fix[p] bit for bit
+ * (+-0.0, subnormals and +-inf are legal held values).  The choice is a select, never arithmetic: a held cell whose v is NaN or inf still
+ * receives d_fix[p], and a free cell receives exactly v.  S(in) reads d_in as it is -- at a held neighbour q it uses d_in[q], not
+ * d_fix[q] -- so after one launch the output holds the held values and after a ping-pong pair both arrays do; a caller who wants the
+ * first launch consistent writes fix's held values into A first (and into B with --time-order 2).  With --residual max, r is max |out - in|
+ * over the whole interior of the stored arrays, held cells included (they contribute +0.0 once d_in holds them).  Only the INTERIOR of
+ * d_fix is read, each value reaching only its own cell; it is never written, must not overlap d_out, and follows the alignment rule of
+ * the other arrays.  Ring fills touch d_in only.
+ * Such a plugin exports drs_plugin_launch_fix / drs_plugin_launch_gold_fix INSTEAD of every other launch entry point: drs_kernel_launch,
+ * _launch_gold, _run, _run_timed and the _src / _res families and drs_kernel_solve return -2 on it, and the five below return -2 on a
+ * kernel generated without --dirichlet, on a null d_fix, and when d_src / d_res do not go with the kernel: d_src is non-null exactly
+ * on a --source kernel, d_res (drs_kernel_residual_elems(k) elements) exactly on a --residual max kernel.  -1 is a HIP error.
+ * --step n > 1, --temporal, --gpus N > 1, --pair-launch 1 and the drs_slab_* runtime refuse --dirichlet. */
+/* drs_kernel_launch / _launch_src / _launch_res with held cells: one launch (in -> out), asynchronous on `stream` */
+int drs_kernel_launch_fix(drs_kernel *k, const void *d_in, void *d_out, const void *d_src, void *d_res, const void *d_fix, void *stream);
+/* drs_kernel_launch_gold / _launch_gold_src with held cells: gold_<name>(in, out[, src], fix), which computes no residual */
+int drs_kernel_launch_gold_fix(drs_kernel *k, const void *d_in, void *d_out, const void *d_src, const void *d_fix, void *stream);
+/* drs_kernel_run / _run_src / _run_res with held cells: the ping-pong loop k(A,B,..,F); k(B,A,..,F) with the same arrays in every launch;
+ * gold != 0 runs gold_<name> (d_res is then left alone).  Returns the launches made. */
+int drs_kernel_run_fix(drs_kernel *k, void *d_a, void *d_b, const void *d_src, void *d_res, const void *d_fix, int iterations, int gold, void *stream);
+/* drs_kernel_run_timed / _run_timed_src / _run_timed_res with held cells: `warmup` launches (A,B), then the loop between two events */
+int drs_kernel_run_timed_fix(drs_kernel *k, void *d_a, void *d_b, const void *d_src, void *d_res, const void *d_fix, int iterations, int warmup, void *stream, float *ms);
+/* drs_kernel_solve with held cells: the same loop and the same answers (0, 1, -4; -2 also on a kernel without --residual max) */
+int drs_kernel_solve_fix(drs_kernel *k, void *d_a, void *d_b, const void *d_src, void *d_res, const void *d_fix, double tol, int max_launches, int check_every_pairs,
+                         void *stream, int *launches, double *residual);
 
 /* ---- N > 1: one rank of a slab-decomposed run (z slabs in 3D, y slabs in 2D), one process per GPU -----------------------------
  * No reference counterpart: the reference is single-GPU (no cudaSetDevice / streams / NCCL anywhere; SURVEY.md section 5 sketches

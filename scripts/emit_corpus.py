@@ -229,8 +229,34 @@ def residual_lists():
     return [(None, l) for l in lists] + [(None, j) for j in residual_cases.all_build_args()]       # what build() emits for the residual tests
 
 
+def dirichlet_lists():
+    """--dirichlet.  Behind everything else, so that the lists in front keep their numbers: against a build without the option `diff -r`
+    shows these files (and --help) and nothing else."""
+    import dirichlet_cases
+    fix3 = ["--3d", "--dtype", "fp32", "--dirichlet", "--check"]
+    lists = [
+        # the emitted main() with the array of held cells, every issue point of the fix stream, all four streams at once, the knob bases
+        fix3 + [stc("t3_wave")], fix3 + ["--store-mask", "buffer", stc("t3_wave")],
+        fix3 + ["--prefetch", "--prefetch-depth", "2", stc("t3_wave")], fix3 + ["--prefetch", "--prefetch-depth", "2", "--store-mask", "buffer", stc("t3_wave")],
+        fix3 + ["--source", "--time-order", "2", "--residual", "max", "--prefetch", "--prefetch-depth", "2", stc("t3_wave")], fix3 + ["--stage", "dma", stc("t3_wave")],
+        fix3 + ["--order", "rows", "--pack", "1", "--block-merge-x", "4", "--defer-stores", "1", "--prefetch", stc("t3_wave")],
+        ["--dtype", "fp64", "--dirichlet", "--time-order", "2", "--check", stc("t2_wave")], ["--dtype", "fp32", "--dirichlet", "--boundary", "reflect", stc("t2_star")],
+        ["--dtype", "fp64", "--dirichlet", "--streaming", "--stage", "dma", stc("t2_star")],
+        # the option has one place in the banner
+        ["--dirichlet", "--3d", "--dirichlet", "--dtype", "fp32", stc("t3_wave")],
+        # rejected before the emitter is asked
+        ["--3d", "--dirichlet", "--step", "2", stc("t3_star")], ["--3d", "--dirichlet", "--step", "2", "--temporal", "1", stc("t3_star")],
+        ["--3d", "--dirichlet", "--temporal", "force", stc("t3_star")], ["--3d", "--dirichlet", "--gpus", "2", stc("t3_star")],
+        ["--3d", "--dirichlet", "--pair-launch", "1", stc("t3_star")],
+    ]
+    for b in ("d3", "d3f64", "rows", "tile", "cross", "stream", "odd"):
+        opts, name = BASES[b]
+        lists.append(list(opts) + ["--dirichlet", stc(name)])
+    return [(None, l) for l in lists] + [(None, j) for j in dirichlet_cases.all_build_args()]       # what build() emits for the dirichlet tests
+
+
 def corpus():
-    return build_lists() + space_sample() + host_lists() + knob_lists() + boundary_lists() + source_lists() + residual_lists()
+    return build_lists() + space_sample() + host_lists() + knob_lists() + boundary_lists() + source_lists() + residual_lists() + dirichlet_lists()
 
 
 def coverage(lists):
