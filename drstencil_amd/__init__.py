@@ -19,6 +19,11 @@ BENCH_DIR = os.path.join(ROOT, "benchmarks")
 _lib = None
 
 
+class Operands(ctypes.Structure):
+    """drs_operands of include/drstencil_amd.h: every array a launch takes beside in and out (device addresses; None where the kernel takes none)."""
+    _fields_ = [("size", ctypes.c_size_t), ("src", ctypes.c_void_p), ("res", ctypes.c_void_p), ("fix", ctypes.c_void_p), ("scale", ctypes.c_void_p)]
+
+
 class NativeLibraryMissing(RuntimeError):
     pass
 
@@ -78,6 +83,12 @@ def lib():
     L.drs_kernel_run_fix.argtypes = [vp, vp, vp, vp, vp, vp, ci, ci, vp]
     L.drs_kernel_run_timed_fix.argtypes = [vp, vp, vp, vp, vp, vp, ci, ci, vp, ctypes.POINTER(ctypes.c_float)]
     L.drs_kernel_solve_fix.argtypes = [vp, vp, vp, vp, vp, vp, ctypes.c_double, ci, ci, vp, ctypes.POINTER(ci), ctypes.POINTER(ctypes.c_double)]
+    op = ctypes.POINTER(Operands)
+    L.drs_kernel_launch_ops.argtypes = [vp, vp, vp, op, vp]
+    L.drs_kernel_launch_gold_ops.argtypes = [vp, vp, vp, op, vp]
+    L.drs_kernel_run_ops.argtypes = [vp, vp, vp, op, ci, ci, vp]
+    L.drs_kernel_run_timed_ops.argtypes = [vp, vp, vp, op, ci, ci, vp, ctypes.POINTER(ctypes.c_float)]
+    L.drs_kernel_solve_ops.argtypes = [vp, vp, vp, op, ctypes.c_double, ci, ci, vp, ctypes.POINTER(ci), ctypes.POINTER(ctypes.c_double)]
     L.drs_kernel_residual.argtypes = [vp, vp, ctypes.POINTER(ctypes.c_double)]
     L.drs_kernel_solve.argtypes = [vp, vp, vp, vp, vp, ctypes.c_double, ci, ci, vp, ctypes.POINTER(ci), ctypes.POINTER(ctypes.c_double)]
     L.drs_slab_unique_id.argtypes = [vp]
@@ -113,6 +124,7 @@ EXPORTS = [
     "drs_kernel_launch_src", "drs_kernel_launch_gold_src", "drs_kernel_run_src", "drs_kernel_run_timed_src",
     "drs_kernel_residual_elems", "drs_kernel_launch_res", "drs_kernel_run_res", "drs_kernel_run_timed_res", "drs_kernel_residual", "drs_kernel_solve",
     "drs_kernel_launch_fix", "drs_kernel_launch_gold_fix", "drs_kernel_run_fix", "drs_kernel_run_timed_fix", "drs_kernel_solve_fix",
+    "drs_kernel_launch_ops", "drs_kernel_launch_gold_ops", "drs_kernel_run_ops", "drs_kernel_run_timed_ops", "drs_kernel_solve_ops",
     "drs_fill_random_f64", "drs_fill_random_f32", "drs_check_error_f64", "drs_check_error_f32",
     "drs_slab_unique_id", "drs_slab_open", "drs_slab_plan", "drs_slab_connect", "drs_slab_run", "drs_slab_sync", "drs_slab_stream", "drs_slab_info",
     "drs_slab_error", "drs_slab_close",
@@ -252,6 +264,32 @@ class Kernel:
             raise ValueError("%s(): d_fix given, but the kernel was generated without --dirichlet" % who)
         return d_fix
 
+    def _scale(self, d_scale, who):
+        """The array of per-cell factors of a call, checked against the kernel: a --scale kernel needs one, any other kernel takes none."""
+        if self.scale and not d_scale:
+            raise ValueError("%s(): the kernel was generated with --scale and needs d_scale, the array of per-cell factors" % who)
+        if not self.scale and d_scale is not None:
+            raise ValueError("%s(): d_scale given, but the kernel was generated without --scale" % who)
+        return d_scale
+
+    def _ops(self, who, d_src, d_res, d_fix, d_scale, gold=False):
+        """The operand block (drs_operands) of a call, every array checked against the kernel (the gold kernel computes no residual)."""
+        return ctypes.byref(Operands(ctypes.sizeof(Operands), self._src(d_src, who), None if gold else self._res(d_res, who), self._fix(d_fix, who),
+                                     self._scale(d_scale, who)))
+
+    @property
+    def scale(self):
+        """True for kernels generated with --scale: a launch takes one more read-only array d_scale (w) of the grid's shape and dtype and
+        computes v = w * S(in) -- with --scale-centre c, v = C * in + w * S(in) -- in front of - out_old, + src and the --dirichlet select,
+        every operation rounded once.  launch, launch_gold, run, run_timed and solve then need the keyword d_scale, the same array for every
+        launch of a loop; such a kernel runs through the operand-block entry points (drs_kernel_*_ops)."""
+        return bool(self.info.get("scale", 0))
+
+    @property
+    def scale_centre(self):
+        """The centre coefficient C of a --scale kernel as the emitted source writes it (0.0: no centre term, also for kernels without --scale)."""
+        return float(self.info.get("scale_centre", 0))
+
     @property
     def dirichlet(self):
         """True for kernels generated with --dirichlet: a launch takes one more read-only array d_fix of the grid's shape and dtype and
@@ -275,13 +313,15 @@ class Kernel:
             raise RuntimeError("HIP error reading the residual")
         return float(v.value)
 
-    def solve(self, d_a, d_b, d_res, tol, max_launches, check_every=8, d_src=None, stream=0, d_fix=None):
+    def solve(self, d_a, d_b, d_res, tol, max_launches, check_every=8, d_src=None, stream=0, d_fix=None, d_scale=None):
         """Run to tolerance (drs_kernel_solve): ping-pong pairs k(A,B); k(B,A), `check_every` pairs between two looks at the residual, until
         it is <= tol.  (status, launches, residual): status 0 converged, 1 max_launches (rounded down to an even number) reached, -4 the
         residual is NaN or inf (a diverged or overflowed run).  The answer is in A.  --dirichlet kernels: d_fix, the held cells (drs_kernel_solve_fix)."""
         self._res(d_res, "solve")
         n, r = ctypes.c_int(), ctypes.c_double()
-        if self._fix(d_fix, "solve"):
+        if self._scale(d_scale, "solve"):
+            rc = lib().drs_kernel_solve_ops(self.h, d_a, d_b, self._ops("solve", d_src, d_res, d_fix, d_scale), tol, max_launches, check_every, stream, ctypes.byref(n), ctypes.byref(r))
+        elif self._fix(d_fix, "solve"):
             rc = lib().drs_kernel_solve_fix(self.h, d_a, d_b, self._src(d_src, "solve"), d_res, d_fix, tol, max_launches, check_every, stream, ctypes.byref(n), ctypes.byref(r))
         else:
             rc = lib().drs_kernel_solve(self.h, d_a, d_b, self._src(d_src, "solve"), d_res, tol, max_launches, check_every, stream, ctypes.byref(n), ctypes.byref(r))
@@ -291,8 +331,10 @@ class Kernel:
             raise RuntimeError("HIP error in drs_kernel_solve")
         return rc, n.value, r.value
 
-    def launch(self, d_in, d_out, stream=0, d_src=None, d_res=None, d_fix=None):
-        if self._fix(d_fix, "launch"):
+    def launch(self, d_in, d_out, stream=0, d_src=None, d_res=None, d_fix=None, d_scale=None):
+        if self._scale(d_scale, "launch"):
+            rc = lib().drs_kernel_launch_ops(self.h, d_in, d_out, self._ops("launch", d_src, d_res, d_fix, d_scale), stream)
+        elif self._fix(d_fix, "launch"):
             rc = lib().drs_kernel_launch_fix(self.h, d_in, d_out, self._src(d_src, "launch"), self._res(d_res, "launch"), d_fix, stream)
         elif self._res(d_res, "launch"):
             rc = lib().drs_kernel_launch_res(self.h, d_in, d_out, self._src(d_src, "launch"), d_res, stream)
@@ -352,8 +394,10 @@ class Kernel:
         if rc != 0:
             raise RuntimeError("HIP launch error %d" % rc)
 
-    def launch_gold(self, d_in, d_out, stream=0, d_src=None, d_fix=None):
-        if self._fix(d_fix, "launch_gold"):
+    def launch_gold(self, d_in, d_out, stream=0, d_src=None, d_fix=None, d_scale=None):
+        if self._scale(d_scale, "launch_gold"):
+            rc = lib().drs_kernel_launch_gold_ops(self.h, d_in, d_out, self._ops("launch_gold", d_src, None, d_fix, d_scale, gold=True), stream)
+        elif self._fix(d_fix, "launch_gold"):
             rc = lib().drs_kernel_launch_gold_fix(self.h, d_in, d_out, self._src(d_src, "launch_gold"), d_fix, stream)
         elif self._src(d_src, "launch_gold"):
             rc = lib().drs_kernel_launch_gold_src(self.h, d_in, d_out, d_src, stream)
@@ -362,12 +406,16 @@ class Kernel:
         if rc != 0:
             raise RuntimeError("HIP launch error %d" % rc)
 
-    def run(self, d_a, d_b, iterations=None, gold=False, stream=0, d_src=None, d_res=None, d_fix=None):
+    def run(self, d_a, d_b, iterations=None, gold=False, stream=0, d_src=None, d_res=None, d_fix=None, d_scale=None):
         """The reference's ping-pong loop (codegen.hpp:581-584); result ends in A.  --source kernels: the same d_src in every launch.
         --residual kernels: d_res[0] then holds the last launch's residual (the gold kernel computes none: gold=True takes no d_res)."""
         it = self.info["iterations"] if iterations is None else iterations
         self._fix(d_fix, "run")
-        if gold and self.residual_elems:
+        if self._scale(d_scale, "run"):
+            if gold and d_res is not None:
+                raise ValueError("run(): the gold kernel computes no residual")
+            n = lib().drs_kernel_run_ops(self.h, d_a, d_b, self._ops("run", d_src, d_res, d_fix, d_scale, gold=gold), it, 1 if gold else 0, stream)
+        elif gold and self.residual_elems:
             # gold_<name> keeps its entry point: the loop is made of single launches
             if d_res is not None:
                 raise ValueError("run(): the gold kernel computes no residual")
@@ -377,7 +425,7 @@ class Kernel:
                 self.launch_gold(d_b, d_a, stream, d_src, d_fix)
                 n += 2
             return n
-        if d_fix:
+        elif d_fix:
             n = lib().drs_kernel_run_fix(self.h, d_a, d_b, self._src(d_src, "run"), self._res(d_res, "run"), d_fix, it, 1 if gold else 0, stream)
         elif self._res(d_res, "run"):
             n = lib().drs_kernel_run_res(self.h, d_a, d_b, self._src(d_src, "run"), d_res, it, stream)
@@ -413,11 +461,13 @@ class Kernel:
             out.append(("top", dim0 - nsl))
         return out
 
-    def run_timed(self, d_a, d_b, iterations=None, warmup=10, stream=0, d_src=None, d_res=None, d_fix=None):
+    def run_timed(self, d_a, d_b, iterations=None, warmup=10, stream=0, d_src=None, d_res=None, d_fix=None, d_scale=None):
         """Warm-up launches + timed loop bracketed by HIP events on `stream`: (launches, ms)."""
         it = self.info["iterations"] if iterations is None else iterations
         ms = ctypes.c_float()
-        if self._fix(d_fix, "run_timed"):
+        if self._scale(d_scale, "run_timed"):
+            n = lib().drs_kernel_run_timed_ops(self.h, d_a, d_b, self._ops("run_timed", d_src, d_res, d_fix, d_scale), it, warmup, stream, ctypes.byref(ms))
+        elif self._fix(d_fix, "run_timed"):
             n = lib().drs_kernel_run_timed_fix(self.h, d_a, d_b, self._src(d_src, "run_timed"), self._res(d_res, "run_timed"), d_fix, it, warmup, stream, ctypes.byref(ms))
         elif self._res(d_res, "run_timed"):
             n = lib().drs_kernel_run_timed_res(self.h, d_a, d_b, self._src(d_src, "run_timed"), d_res, it, warmup, stream, ctypes.byref(ms))
@@ -451,7 +501,8 @@ class Kernel:
         # --time-order 2 also reads the old output, --source the source array: one more whole array each is the algorithmic minimum (the centre
         # values of --residual are cells the sweep reads anyway)
         # --dirichlet reads the array of held cells: one more whole array
-        return (2 + (self.time_order == 2) + self.source + self.dirichlet) * (4 if i["dtype"] == "fp32" else 8) * pts
+        # --scale reads the array of factors: one more whole array (the centre values of --scale-centre are cached re-reads, as --residual's)
+        return (2 + (self.time_order == 2) + self.source + self.dirichlet + self.scale) * (4 if i["dtype"] == "fp32" else 8) * pts
 
     # ---- placement of the output array (csrc/schedule.hpp: Schedule::out_skew_bytes; profiles/r03_probe_skew4.log) ----
     def array_bytes(self):

@@ -42,8 +42,11 @@ struct drs_kernel {
     // --dirichlet kernels: these two, with every array in their signatures (src / res null unless --source / --residual), INSTEAD of all the others
     int (*launch_fix)(const void *, void *, const void *, void *, const void *, hipStream_t) = nullptr;
     int (*launch_gold_fix)(const void *, void *, const void *, const void *, hipStream_t) = nullptr;
+    // --scale kernels: these two, with every array in their signatures (null where the option is off), INSTEAD of all the others
+    int (*launch_ops)(const void *, void *, const void *, void *, const void *, const void *, hipStream_t) = nullptr;
+    int (*launch_gold_ops)(const void *, void *, const void *, const void *, const void *, hipStream_t) = nullptr;
     long residual_elems = 0;     // elements of d_res (1 + launched workgroups); 0: no --residual
-    bool has_source = false, fp32 = false;
+    bool has_source = false, has_fix = false, has_scale = false, fp32 = false;
     int (*wrap)(void *, hipStream_t) = nullptr;              // only with a non-fixed boundary (--boundary periodic / reflect, --boundary-x / -y / -z)
     const char *(*info)(void) = nullptr;
     std::string path;
@@ -354,7 +357,11 @@ drs_kernel *drs_kernel_build(int argc, const char *const *argv, const char *cach
     k->launch_res = (int (*)(const void *, void *, const void *, void *, hipStream_t))dlsym(dl, "drs_plugin_launch_res");
     k->launch_fix = (int (*)(const void *, void *, const void *, void *, const void *, hipStream_t))dlsym(dl, "drs_plugin_launch_fix");
     k->launch_gold_fix = (int (*)(const void *, void *, const void *, const void *, hipStream_t))dlsym(dl, "drs_plugin_launch_gold_fix");
+    k->launch_ops = (int (*)(const void *, void *, const void *, void *, const void *, const void *, hipStream_t))dlsym(dl, "drs_plugin_launch_ops");
+    k->launch_gold_ops = (int (*)(const void *, void *, const void *, const void *, const void *, hipStream_t))dlsym(dl, "drs_plugin_launch_gold_ops");
     k->has_source = r.plan.source;
+    k->has_fix = r.plan.dirichlet;
+    k->has_scale = r.plan.scale;
     k->fp32 = r.plan.fp32;
     k->residual_elems = r.plan.residual ? Schedule(r.plan, r.opt).residual_elems() : 0;
     k->wrap = (int (*)(void *, hipStream_t))dlsym(dl, "drs_plugin_wrap");
@@ -374,8 +381,10 @@ drs_kernel *drs_kernel_build(int argc, const char *const *argv, const char *cach
     // --dirichlet: its two entry points and none of the others
     const bool others = k->launch || k->launch_gold || k->launch_src || k->launch_gold_src || k->launch_res;
     const bool with_fix = k->launch_fix && k->launch_gold_fix && !others;
-    const bool fix_ok = r.plan.dirichlet ? with_fix : (!k->launch_fix && !k->launch_gold_fix);
-    if (!fix_ok || (!r.plan.dirichlet && (!(plain || with_src) || with_src != r.plan.source)) || !k->info) {
+    // --scale: its two entry points and none of the others, --dirichlet's included
+    const bool with_ops = k->launch_ops && k->launch_gold_ops && !others && !k->launch_fix && !k->launch_gold_fix;
+    const bool fix_ok = r.plan.scale ? with_ops : (!k->launch_ops && !k->launch_gold_ops && (r.plan.dirichlet ? with_fix : (!k->launch_fix && !k->launch_gold_fix)));
+    if (!fix_ok || (!r.plan.dirichlet && !r.plan.scale && (!(plain || with_src) || with_src != r.plan.source)) || !k->info) {
         if (log) *log = dup_cstr("plugin " + so + " lacks the drs_plugin_* entry points\n");
         dlclose(dl);
         delete k;
@@ -651,6 +660,100 @@ int drs_kernel_solve_fix(drs_kernel *k, void *d_a, void *d_b, const void *d_src,
         }
         n += 2 * pairs;
         if (hipStreamSynchronize((hipStream_t)stream) != hipSuccess || !read_residual(k, d_res, &r)) return -1;
+        if (launches) *launches = n;
+        if (residual) *residual = r;
+        if (std::isnan(r) || std::isinf(r)) return -4;       // diverged or overflowed: reported, not iterated on
+        if (r <= tol) return 0;
+    }
+    return 1;
+}
+
+// ---- the operand block: one family of entry points for every kernel, whatever arrays it takes ----------------------------------------------
+// ops->size is checked; a pointer the kernel needs must be non-null and a pointer it does not take must be null, else -2 (the gold kernel
+// computes no residual: the gold forms leave ops->res alone, and take it only on a --residual max kernel)
+namespace {
+struct Operands { const void *src = nullptr; void *res = nullptr; const void *fix = nullptr; const void *scale = nullptr; };
+bool ops_ok(const drs_kernel *k, const drs_operands *ops, bool gold, Operands &v) {
+    if (!k || !ops || ops->size != sizeof(drs_operands)) return false;
+    v.src = ops->src; v.res = ops->res; v.fix = ops->fix; v.scale = ops->scale;
+    if ((v.src != nullptr) != k->has_source || (v.fix != nullptr) != k->has_fix || (v.scale != nullptr) != k->has_scale) return false;
+    if (gold) return k->residual_elems ? true : v.res == nullptr;
+    return (v.res != nullptr) == (k->residual_elems != 0);
+}
+// one launch through whichever entry points the plugin exports
+int ops_one(drs_kernel *k, const void *in, void *out, const Operands &v, bool gold, hipStream_t s) {
+    if (k->has_scale) return gold ? k->launch_gold_ops(in, out, v.src, v.fix, v.scale, s) : k->launch_ops(in, out, v.src, v.res, v.fix, v.scale, s);
+    if (k->has_fix) return gold ? k->launch_gold_fix(in, out, v.src, v.fix, s) : k->launch_fix(in, out, v.src, v.res, v.fix, s);
+    if (gold) return v.src ? k->launch_gold_src(in, out, v.src, s) : k->launch_gold(in, out, s);
+    if (k->residual_elems) return k->launch_res(in, out, v.src, v.res, s);
+    return v.src ? k->launch_src(in, out, v.src, s) : k->launch(in, out, s);
+}
+int ops_loop(drs_kernel *k, void *d_a, void *d_b, const Operands &v, int iterations, bool gold, hipStream_t s) {
+    g_launched = true;
+    int n = 0;
+    for (int t = 0; t < iterations; t += 2 * k->step) {
+        if (ops_one(k, d_a, d_b, v, gold, s) != 0) return -1;
+        if (ops_one(k, d_b, d_a, v, gold, s) != 0) return -1;
+        n += 2;
+    }
+    return n;
+}
+}  // namespace
+int drs_kernel_launch_ops(drs_kernel *k, const void *d_in, void *d_out, const drs_operands *ops, void *stream) {
+    Operands v;
+    if (!ops_ok(k, ops, false, v)) return -2;
+    g_launched = true;
+    return ops_one(k, d_in, d_out, v, false, (hipStream_t)stream);
+}
+int drs_kernel_launch_gold_ops(drs_kernel *k, const void *d_in, void *d_out, const drs_operands *ops, void *stream) {
+    Operands v;
+    if (!ops_ok(k, ops, true, v)) return -2;
+    g_launched = true;
+    return ops_one(k, d_in, d_out, v, true, (hipStream_t)stream);
+}
+int drs_kernel_run_ops(drs_kernel *k, void *d_a, void *d_b, const drs_operands *ops, int iterations, int gold, void *stream) {
+    Operands v;
+    if (!ops_ok(k, ops, gold != 0, v)) return -2;
+    if (!gold && k->horizon >= 0 && !k->forced && iterations > k->horizon) return -3;      // as drs_kernel_run
+    return ops_loop(k, d_a, d_b, v, iterations, gold != 0, (hipStream_t)stream);
+}
+int drs_kernel_run_timed_ops(drs_kernel *k, void *d_a, void *d_b, const drs_operands *ops, int iterations, int warmup, void *stream, float *ms) {
+    Operands v;
+    if (!ops_ok(k, ops, false, v)) return -2;
+    if (k->horizon >= 0 && !k->forced && iterations > k->horizon) return -3;
+    hipStream_t s = (hipStream_t)stream;
+    g_launched = true;
+    for (int i = 0; i < warmup; i++)
+        if (ops_one(k, d_a, d_b, v, false, s) != 0) return -1;
+    hipEvent_t e0, e1;
+    if (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess) return -1;
+    (void)hipEventRecord(e0, s);
+    const int n = ops_loop(k, d_a, d_b, v, iterations, false, s);
+    (void)hipEventRecord(e1, s);
+    hipError_t err = hipEventSynchronize(e1);
+    float t = 0.f;
+    if (err == hipSuccess) err = hipEventElapsedTime(&t, e0, e1);
+    (void)hipEventDestroy(e0);
+    (void)hipEventDestroy(e1);
+    if (ms) *ms = t;
+    return (err == hipSuccess) ? n : -1;
+}
+// drs_kernel_solve through the operand block: the same loop, the same answers; -2 also on a kernel without --residual max
+int drs_kernel_solve_ops(drs_kernel *k, void *d_a, void *d_b, const drs_operands *ops, double tol, int max_launches, int check_every_pairs, void *stream,
+                         int *launches, double *residual) {
+    if (launches) *launches = 0;
+    if (residual) *residual = std::nan("");
+    Operands v;
+    if (!ops_ok(k, ops, false, v) || !k->residual_elems || check_every_pairs < 1) return -2;
+    const int limit = max_launches < 0 ? 0 : max_launches - max_launches % 2;
+    int n = 0;
+    double r = std::nan("");
+    g_launched = true;
+    while (n < limit) {
+        const int pairs = std::min(check_every_pairs, (limit - n) / 2);
+        if (ops_loop(k, d_a, d_b, v, 2 * pairs * k->step, false, (hipStream_t)stream) != 2 * pairs) return -1;
+        n += 2 * pairs;
+        if (hipStreamSynchronize((hipStream_t)stream) != hipSuccess || !read_residual(k, v.res, &r)) return -1;
         if (launches) *launches = n;
         if (residual) *residual = r;
         if (std::isnan(r) || std::isinf(r)) return -4;       // diverged or overflowed: reported, not iterated on

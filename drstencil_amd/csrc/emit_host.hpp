@@ -26,7 +26,7 @@ inline std::string check_call(const KernelPlan &p, const std::string &outer) {
 inline std::string gold_kernel(const KernelPlan &p) {
     std::ostringstream g;
     g << "// naive reference kernel: the verification arithmetic (same term order, same FMA chain)\n";
-    g << "extern \"C\" __global__ void gold_" << p.name << " (const real_t* __restrict__ d_in, real_t* __restrict__ d_out" << (p.source ? ", const real_t* __restrict__ d_src" : "") << (p.dirichlet ? ", const real_t* __restrict__ d_fix" : "") << ")\n{\n";
+    g << "extern \"C\" __global__ void gold_" << p.name << " (const real_t* __restrict__ d_in, real_t* __restrict__ d_out" << (p.source ? ", const real_t* __restrict__ d_src" : "") << (p.dirichlet ? ", const real_t* __restrict__ d_fix" : "") << (p.scale ? ", const real_t* __restrict__ d_scale" : "") << ")\n{\n";
     g << "    const int i = (int)(blockIdx.x * blockDim.x + threadIdx.x);\n";
     g << "    const int j = (int)(blockIdx.y * blockDim.y + threadIdx.y);\n";
     if (p.ndim == 3) g << "    const int k = (int)(blockIdx.z * blockDim.z + threadIdx.z);\n";
@@ -46,7 +46,14 @@ inline std::string gold_kernel(const KernelPlan &p) {
         first = false;
     }
     const std::string gidx = p.ndim == 3 ? "((long)k * M + j) * N + i" : "(long)j * N + i";
-    if (p.dirichlet) {   // explicit statements, in the sweep's order; the last one is a select, never arithmetic: a held cell receives fix bit for bit
+    if (p.scale) {       // explicit statements, in the sweep's order, each a rounded operation of its own: w *, [C * in +,] [- old,] [+ src,] [select]
+        g << "        t = d_scale[" << gidx << "] * t;\n";
+        if (p.centre_term()) g << "        { const real_t u = (real_t)(" << p.scale_centre << ") * c[0]; t = u + t; }\n";
+        if (p.second_order) g << "        t = t - d_out[" << gidx << "];\n";
+        if (p.source) g << "        t = t + d_src[" << gidx << "];\n";
+        if (p.dirichlet) g << "        { const real_t f = d_fix[" << gidx << "]; t = (f != f) ? t : f; }\n";
+        g << "        d_out[" << gidx << "] = t;\n";
+    } else if (p.dirichlet) {   // explicit statements, in the sweep's order; the last one is a select, never arithmetic: a held cell receives fix bit for bit
         if (p.second_order) g << "        t = t - d_out[" << gidx << "];\n";
         if (p.source) g << "        t = t + d_src[" << gidx << "];\n";
         g << "        const real_t f = d_fix[" << gidx << "];\n";
@@ -170,6 +177,7 @@ inline std::string info_json(const Schedule &s) {
     if (p.second_order) j.insert(j.size() - 1, ",\\\"time_order\\\":2");
     if (p.source) j.insert(j.size() - 1, ",\\\"source\\\":1");
     if (p.dirichlet) j.insert(j.size() - 1, ",\\\"dirichlet\\\":1");
+    if (p.scale) j.insert(j.size() - 1, sfmt(",\\\"scale\\\":1,\\\"scale_centre\\\":%s", p.centre_term() ? p.scale_centre.c_str() : "0"));
     if (p.residual) j.insert(j.size() - 1, sfmt(",\\\"residual\\\":\\\"max\\\",\\\"residual_elems\\\":%ld", s.residual_elems()));
     if (p.periodic) {
         const int H = p.halo;
@@ -197,6 +205,27 @@ inline std::string plugin_api(const Schedule &s) {
     const std::string wrap_in = p.fills_ring() ? "    if (int rc = drs_plugin_wrap((void*)in, stream)) return rc;\n" : "";
     // --source kernels take three arrays: they export the _src entry points INSTEAD of the two-pointer ones
     const std::string sfx = p.source ? "_src" : "", src_par = p.source ? ", const void* src" : "", src_arg = p.source ? ", (const real_t*)src" : "";
+    if (p.scale) {
+        // --scale kernels export these two INSTEAD of every other launch entry point, with every array in their signatures: src is null unless
+        // --source, res unless --residual max, fix unless --dirichlet
+        const std::string res_arg = p.residual ? ", (real_t*)res" : "", fix_arg = p.dirichlet ? ", (const real_t*)fix" : "";
+        a << "extern \"C\" int drs_plugin_launch_ops(const void* in, void* out, const void* src, void* res, const void* fix, const void* scale, hipStream_t stream)\n{\n" << wrap_in;
+        if (!p.source) a << "    (void)src;\n";
+        if (!p.residual) a << "    (void)res;\n";
+        if (!p.dirichlet) a << "    (void)fix;\n";
+        a << "    hipLaunchKernelGGL(dr_" << p.name << ", dim3(DRS_GRID), dim3(DRS_NTL), 0, stream, (const real_t*)in, (real_t*)out" << src_arg << res_arg << fix_arg << ", (const real_t*)scale);\n";
+        if (p.residual) a << "    hipLaunchKernelGGL(res_" << p.name << ", dim3(1), dim3(256), 0, stream, (real_t*)res);\n";
+        a << "    return (int)hipGetLastError();\n}\n";
+        a << "extern \"C\" int drs_plugin_launch_gold_ops(const void* in, void* out, const void* src, const void* fix, const void* scale, hipStream_t stream)\n{\n" << wrap_in;
+        if (!p.source) a << "    (void)src;\n";
+        if (!p.dirichlet) a << "    (void)fix;\n";
+        if (p.ndim == 3) a << "    dim3 b(64, 2, 2), g((N + 63) / 64, (M + 1) / 2, (L + 1) / 2);\n";
+        else a << "    dim3 b(64, 4, 1), g((N + 63) / 64, (M + 3) / 4, 1);\n";
+        a << "    hipLaunchKernelGGL(gold_" << p.name << ", g, b, 0, stream, (const real_t*)in, (real_t*)out" << src_arg << fix_arg << ", (const real_t*)scale);\n";
+        a << "    return (int)hipGetLastError();\n}\n";
+        a << "extern \"C\" const char* drs_plugin_info(void)\n{\n    return \"" << info_json(s) << "\";\n}\n\n";
+        return a.str();
+    }
     if (p.dirichlet) {
         // --dirichlet kernels export these two INSTEAD of every other launch entry point, with every array in their signatures: src is null
         // unless --source, res unless --residual max (then res_<name> folds the partials behind the sweep, on the same stream)
@@ -630,11 +659,12 @@ inline std::string host_main(const Schedule &s) {
     if (p.second_order) h << "    real_t* h_in = getRandomArray<real_t> (npoints);\n    real_t* h_out = getRandomArray<real_t> (npoints);   // time order 2: out holds u(t-1), input too (the rand() sequence continued)\n";
     else h << "    real_t* h_in = getRandomArray<real_t> (npoints);\n    real_t* h_out = getZeroArray<real_t> (npoints);\n";
     // --source: the third array continues the reference's rand() fill behind the arrays filled today; it lies behind the pair in the same arena
-    const std::string launch = p.dirichlet ? "drs_plugin_launch_fix" : p.residual ? "drs_plugin_launch_res" : p.source ? "drs_plugin_launch_src" : "drs_plugin_launch",
-                      gold = p.dirichlet ? "drs_plugin_launch_gold_fix" : p.source ? "drs_plugin_launch_gold_src" : "drs_plugin_launch_gold";
-    // --dirichlet: every array in both signatures, NULL where its option is off
-    const std::string gsarg = p.dirichlet ? std::string(p.source ? ", src" : ", NULL") + ", d_fix" : p.source ? ", src" : "";       // the gold kernel computes no residual
-    const std::string sarg = p.dirichlet ? std::string(p.source ? ", src" : ", NULL") + (p.residual ? ", d_res" : ", NULL") + ", d_fix"
+    const std::string launch = p.scale ? "drs_plugin_launch_ops" : p.dirichlet ? "drs_plugin_launch_fix" : p.residual ? "drs_plugin_launch_res" : p.source ? "drs_plugin_launch_src" : "drs_plugin_launch",
+                      gold = p.scale ? "drs_plugin_launch_gold_ops" : p.dirichlet ? "drs_plugin_launch_gold_fix" : p.source ? "drs_plugin_launch_gold_src" : "drs_plugin_launch_gold";
+    // --dirichlet and --scale: every array in both signatures, NULL where its option is off
+    const std::string gsarg = p.scale ? std::string(p.source ? ", src" : ", NULL") + (p.dirichlet ? ", d_fix" : ", NULL") + ", d_scale" : p.dirichlet ? std::string(p.source ? ", src" : ", NULL") + ", d_fix" : p.source ? ", src" : "";       // the gold kernel computes no residual
+    const std::string sarg = p.scale ? std::string(p.source ? ", src" : ", NULL") + (p.residual ? ", d_res" : ", NULL") + (p.dirichlet ? ", d_fix" : ", NULL") + ", d_scale"
+                           : p.dirichlet ? std::string(p.source ? ", src" : ", NULL") + (p.residual ? ", d_res" : ", NULL") + ", d_fix"
                                          : p.residual ? (p.source ? ", src, d_res" : ", NULL, d_res") : gsarg;
     if (p.source) h << "    real_t* h_src = getRandomArray<real_t> (npoints);   // the source term (the rand() sequence continued)\n";
     h << "    // both arrays in ONE allocation, the output " << (s.out_skew_bytes() >> 20) << " MiB (mod " << (Schedule::kPlacementPeriod >> 20) << " MiB) behind the input: launch time depends on (out - in) mod 64 MiB (--out-skew)\n";
@@ -656,6 +686,13 @@ inline std::string host_main(const Schedule &s) {
              "    for (size_t x = 0; x < npoints; x++) if (!(h_fix[x] < (real_t)0.25)) h_fix[x] = (real_t)__builtin_nan (\"\");\n"
              "    real_t *d_fix;\n    (void)hipMalloc (&d_fix, nbytes);\n    check_error (\"Failed to allocate device memory for fix.\\n\");\n"
              "    (void)hipMemcpy (d_fix, h_fix, nbytes, hipMemcpyHostToDevice);\n";
+    if (p.scale)
+        // the array of factors continues the rand() fill behind every other array, mapped into [0.5, 1): a contraction for every stencil whose
+        // taps' magnitudes sum to at most 1.  An allocation of its own, so that the other arrays' places stay as they are
+        h << "    real_t* h_scale = getRandomArray<real_t> (npoints);   // --scale (the rand() sequence continued): factors in [0.5, 1)\n"
+             "    for (size_t x = 0; x < npoints; x++) h_scale[x] = (real_t)0.5 + (real_t)0.5 * h_scale[x];\n"
+             "    real_t *d_scale;\n    (void)hipMalloc (&d_scale, nbytes);\n    check_error (\"Failed to allocate device memory for scale.\\n\");\n"
+             "    (void)hipMemcpy (d_scale, h_scale, nbytes, hipMemcpyHostToDevice);\n";
     if (p.residual) h << "    real_t *d_res;   // --residual: [0] the last launch's max |out - in|, then one partial per workgroup; written whole by every launch\n"
                          "    (void)hipMalloc (&d_res, sizeof(real_t) * DRS_RES_ELEMS);\n    check_error (\"Failed to allocate device memory for the residual.\\n\");\n";
     h << "    puts(\"GPU computing ...\");\n\n    // warm up\n    for (int i = 0; i < 10; i ++) " << launch << " (in, out" << sarg << ", 0);\n\n";
@@ -704,6 +741,7 @@ inline std::string host_main(const Schedule &s) {
     if (p.source) h << "\n    delete[] h_src;";
     if (p.residual) h << "\n    (void)hipFree (d_res);";
     if (p.dirichlet) h << "\n    delete[] h_fix;\n    (void)hipFree (d_fix);";
+    if (p.scale) h << "\n    delete[] h_scale;\n    (void)hipFree (d_scale);";
     h << "\n    delete[] h_in;\n    delete[] h_out;\n    (void)hipFree (arena);\n    return 0;\n}\n#endif\n";
     return h.str();
 }

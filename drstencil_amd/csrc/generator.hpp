@@ -154,6 +154,19 @@ MI355X options:
                         sees the selected value.  The kernel is dr_<name>(in, out, [src,] [res,] fix) and the plugin exports
                         drs_plugin_launch_fix / drs_plugin_launch_gold_fix instead of the other launch entry points.  Needs --step 1; not with
                         --temporal, --gpus N > 1 or --pair-launch 1.
+--scale                 A per-cell factor: a launch takes one more array w of the grid's shape and dtype and computes, at every interior
+                        point p, v = w[p] * S(in)[p] -- one rounded multiplication on the unchanged FMA chain -- in front of - out_old
+                        (--time-order 2), + src (--source) and the --dirichlet select.  w is read in the interior only and never written; it
+                        must not overlap out; the same w goes to every launch.  With w = 1 everywhere the stored bits are those of the same
+                        command without the option.  The kernel is dr_<name>(in, out, [src,] [res,] [fix,] w) and the plugin exports
+                        drs_plugin_launch_ops / drs_plugin_launch_gold_ops instead of the other launch entry points.  Needs --step 1; not
+                        with --temporal, --gpus N > 1 or --pair-launch 1.
+--scale-centre <c>      With --scale: v = C * in[p] + w[p] * S(in)[p], a rounded product and a rounded sum behind the multiplication by w,
+                        nothing contracted.  C is c as a coefficient of the .stc is written (six digits, cast to the dtype); c is a finite
+                        real, default 0 (no centre term).  With S = L, a stencil whose taps sum to 0:
+                          heterogeneous diffusion  u' = u + k*L(u)            --scale --scale-centre 1, w = kappa*dt/h^2
+                          wave, velocity model     u' = 2u + v*L(u) - u_old   --scale --scale-centre 2 --time-order 2, w = v^2*dt^2/h^2
+                          Jacobi, variable diagonal u' = A(u)/d + f/d          --scale --source, S the off-diagonal average, w = 1/diag, src = f/diag
 --xrim <lds|dpp>        x halo inside a wavefront by DPP wave shifts (default) or through LDS.
 --schedule <scatter|reuse|window>  How reuse along the streamed dimension is split between source planes kept on chip and
                         partial sums carried in VGPRs (results never depend on it):
@@ -276,6 +289,15 @@ inline bool put_temporal(GenOptions &o, const std::string &v) {
     if (t >= 0) o.temporal = t;
     return t >= 0;
 }
+// --scale-centre <c>: a finite real, the whole word
+inline bool put_scale_centre(GenOptions &o, const std::string &v) {
+    char *end = nullptr;
+    const double c = strtod(v.c_str(), &end);
+    if (v.empty() || *end || !std::isfinite(c)) return false;
+    o.scale_centre = c;
+    o.scale_centre_set = true;
+    return true;
+}
 inline bool put_cc_opt(GenOptions &o, const std::string &v) { o.cc_opts.push_back(v); return true; }
 
 inline constexpr Opt kOptions[] = {
@@ -294,6 +316,7 @@ inline constexpr Opt kOptions[] = {
     {"--boundary-z", &GenOptions::boundary_z, "fixed periodic reflect", NAMES, &GenOptions::boundary_z_set},
     {"--time-order", &GenOptions::time_order, NAMES}, {"--source", &GenOptions::source, NAMES},
     {"--residual", &GenOptions::residual, "max", NAMES, &GenOptions::residual_set}, {"--dirichlet", &GenOptions::dirichlet, NAMES},
+    {"--scale", &GenOptions::scale, NAMES}, {"--scale-centre", put_scale_centre, NAMES},
     {"--gpus", &GenOptions::gpus, NAMES | LOCAL}, {"--pair-launch", &GenOptions::pair_launch, NAMES}, {"--temporal", put_temporal, NAMES},
     {"--out-skew", &GenOptions::out_skew, NAMES}, {"--tuned-defaults", &GenOptions::tuned_defaults, NAMES},
     {"--schedule", &GenOptions::schedule, "scatter reuse window", 0, &GenOptions::schedule_set},
@@ -360,6 +383,7 @@ inline bool scan_options(const std::vector<std::string> &args, GenResult &res, s
         }
         if (a == "--time-order" && o.time_order == 1) continue;       // likewise
         if (a == "--dirichlet") continue;                             // echoed once, behind every other option (below)
+        if (a == "--scale" || a == "--scale-centre") continue;        // likewise, behind --dirichlet
         echo(a, !(r->attr & LOCAL));
         if (!flag) echo(v, !(r->attr & LOCAL));
     }
@@ -376,6 +400,11 @@ inline bool scan_options(const std::vector<std::string> &args, GenResult &res, s
         for (auto &w : boundary_words(o.is3d ? 3 : 2, m)) words.insert(words.begin() + at++, {w, true, true});
     }
     if (o.dirichlet) words.push_back({"--dirichlet", true, false});     // its canonical place: wherever and however often it stood, the same command
+    if (o.scale) words.push_back({"--scale", true, false});
+    if (o.scale_centre_set && !(o.scale && coef_rounded(o.scale_centre) == 0.0)) {       // the coefficient as the source writes it; c = 0 is the default spelled out and leaves no trace
+        words.push_back({"--scale-centre", true, false});
+        words.push_back({coef_text(o.scale_centre), true, false});
+    }
     for (auto &e : words) { banner += (banner.empty() ? "" : " ") + e.w; if (e.slab) o.slab_args.push_back(e.w); }
     return true;
 }
@@ -466,6 +495,13 @@ inline GenResult generate(const std::vector<std::string> &args /* argv[1..] */) 
                                : "--dirichlet cannot be combined with --pair-launch 1 (the pair kernel serves the slab runtime, which has no held cells)";
         return res;
     }
+    if (res.plan.scale && (o.gpus > 1 || o.pair_launch)) {
+        // the slab views are windows of two arrays; a view of the array of factors is no part of the slab runtime, and the pair kernel serves it
+        res.messages += "Invalid configuration!\n"; res.exit_code = 255;
+        res.error = o.gpus > 1 ? "--scale cannot be combined with --gpus N > 1 (the slab runtime passes no view of an array of factors)"
+                               : "--scale cannot be combined with --pair-launch 1 (the pair kernel serves the slab runtime, which has no per-cell factor)";
+        return res;
+    }
     const Schedule sched(res.plan, o);
     if (!sched.config_error().empty()) { res.messages += "Invalid configuration!\n"; res.exit_code = 255; res.error = sched.config_error(); return res; }
     if (sched.lds_bytes() > 160 * 1024) {   // gfx950: 160 KiB of LDS per workgroup
@@ -510,6 +546,9 @@ inline GenResult generate(const std::vector<std::string> &args /* argv[1..] */) 
         res.notes += "drstencil: note: residual: a launch takes one more array of " + std::to_string(sched.residual_elems()) + " elements and writes r = max |out - in| over the interior to its first element (NaN if any term is NaN)\n";
     if (res.plan.dirichlet)
         res.notes += "drstencil: note: held cells: a launch takes one more array fix and stores fix[p] wherever it is not NaN, else the computed value (fix is read only, in its interior)\n";
+    if (res.plan.scale)
+        res.notes += std::string("drstencil: note: per-cell factor: a launch takes one more array w and computes ") +
+                     (res.plan.centre_term() ? "(" + res.plan.scale_centre + ") * in + w * S(in)" : std::string("w * S(in)")) + " on the interior, in front of the other options' operations (w is read only, in its interior)\n";
     if (!res.tuned_from.empty())
         res.notes += "drstencil: note: no geometry option given: the tuner's configuration for this stencil, step, dtype and grid size is used (" +
                      res.tuned_from + "); --tuned-defaults 0 keeps the generic defaults\n";

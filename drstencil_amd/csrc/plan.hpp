@@ -194,6 +194,12 @@ struct GenOptions {
                                  // out[p] = (fix[p] != fix[p]) ? v : fix[p], v the value the same command without the option would store: a cell
                                  // whose fix is NaN is free, every other cell is held at fix[p], bit for bit.  A select, never arithmetic.  fix is
                                  // one more memory stream of the sweep, read once.  It names the problem, not a tuning choice
+    bool scale = false;          // --scale: a launch takes one more read-only array w of the grid's shape and dtype and computes
+                                 // v = w[p] * S(in)[p] (one rounded multiplication on the finished FMA chain) in front of - out_old, + src and the
+                                 // --dirichlet select.  w is one more memory stream of the sweep, read once.  It names the problem, not a tuning choice
+    double scale_centre = 0.0;   // --scale-centre c (needs --scale): v = C * in[p] + w[p] * S(in)[p], a rounded product and a rounded sum, C being c as
+                                 // the emitted source writes coefficients (coef_text).  0: no centre term, the centre values are not loaded for it
+    bool scale_centre_set = false;
 };
 
 // ---- boundary modes per axis (0 z, 1 y, 2 x; z counts as fixed in 2D)
@@ -268,6 +274,10 @@ struct KernelPlan {
     bool source = false;         // --source: out = S(in) + src (order 2: (S(in) - out_old) + src) on the interior; src's interior is read, each value reaching only its own cell
     bool residual = false;       // --residual max: the launch also writes r = max |out - in| over the interior (NaN if any term is NaN) to d_res[0]
     bool dirichlet = false;      // --dirichlet: out = fix where fix is not NaN (held cells), else the value computed as without the option; fix's interior is read, each value reaching only its own cell
+    bool scale = false;          // --scale: v = w * S(in) on the interior, in front of every other stream's operation; w's interior is read, each value reaching only its own cell
+    std::string scale_centre;    // --scale-centre c != 0: the coefficient's text (coef_text), v = C * in + w * S(in); empty: no centre term
+    bool centre_term() const { return !scale_centre.empty(); }
+    bool centre_live() const { return residual || centre_term(); }      // the input's centre values are a stream of the sweep (one family of sets, whoever needs them)
     std::string error;       // non-empty: invalid configuration
     std::string note;        // non-empty: something the user asked for was not done (printed by the generator, kept in the banner)
 };

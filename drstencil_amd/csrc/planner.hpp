@@ -302,6 +302,12 @@ inline KernelPlan make_plan(const Stencil &st, const GenOptions &o_in, const std
     p.dirichlet = o.dirichlet;
     if (p.dirichlet && o_in.step > 1) { p.error = "--dirichlet needs --step 1 (a fused S^n through held cells is not n held steps)"; return p; }
     if (p.dirichlet && o_in.temporal) { p.error = "--dirichlet cannot be combined with --temporal (on-chip stages fuse time steps; every held step re-imposes the held cells)"; return p; }
+    // --scale: the factor multiplies one step's S(in); S^n(in) scaled once is not n scaled steps, fused or staged
+    p.scale = o.scale;
+    if (o.scale_centre_set && !o.scale) { p.error = "--scale-centre needs --scale (the centre term goes with the per-cell factor: out = c*in + w*S(in))"; return p; }
+    if (p.scale && o_in.step > 1) { p.error = "--scale needs --step 1 (a fused S^n scaled once is not n scaled steps)"; return p; }
+    if (p.scale && o_in.temporal) { p.error = "--scale cannot be combined with --temporal (on-chip stages fuse time steps; every scaled step multiplies by the factor)"; return p; }
+    if (p.scale && coef_rounded(o.scale_centre) != 0.0) p.scale_centre = coef_text(o.scale_centre);
     if (p.residual && o_in.temporal) { p.error = "--residual cannot be combined with --temporal (on-chip stages keep the intermediate steps on the chip: the sweep that stores never holds the input's centre values)"; return p; }
 
     if (o.loader_waves > 0 && o.stage != "dma") { p.error = "--loader-waves goes with --stage dma"; return p; }

@@ -94,10 +94,13 @@ struct Schedule {
     // wavefront through the LDS image, which is free by then) and writes ONE partial, d_res[1 + blockIdx.x]; res_<name> folds them.
     // ---- --dirichlet: fix is a fourth stream of that kind, from its own array: out = fix where fix is not NaN.  It joins the count: the
     // same distance, its own family of register sets (fv<set>_<r>_<q>), and emit_final selects with it after the other two are applied.
-    int extra_streams() const { return (p.second_order ? 1 : 0) + (p.source ? 1 : 0) + (p.dirichlet ? 1 : 0); }
+    // ---- --scale: w is a fifth stream of that kind, from its own array: v = w * S(in), applied first (wv<set>_<r>_<q>).  --scale-centre c
+    // makes the centre sets live exactly as --residual does (v = C * in + w * S(in)); with both options there is ONE family of centre
+    // sets, loaded once, and residual_words() counts it once.
+    int extra_streams() const { return (p.second_order ? 1 : 0) + (p.source ? 1 : 0) + (p.dirichlet ? 1 : 0) + (p.scale ? 1 : 0); }
     int old_dist() const { return ((extra_streams() || p.residual) && p.prefetch && p.has_s && !p.dma) ? PD : 0; }
     int old_sets() const { return old_dist() + 1; }
-    int residual_words() const { return p.residual ? old_sets() * p.RY * p.VX + 1 : 0; }      // elements: the centre sets and rmax
+    int residual_words() const { return (p.centre_live() ? old_sets() * p.RY * p.VX : 0) + (p.residual ? 1 : 0); }      // elements: the centre sets (--residual, --scale-centre: one family) and rmax
     long residual_elems() const { return p.residual ? 1L + grid_size() : 0L; }                // d_res: the result, then one partial per launched workgroup
     int reg_demand_sweep() const {
         const int words = p.fp32 ? 1 : 2, pts = p.RY * p.VX;

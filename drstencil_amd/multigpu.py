@@ -83,6 +83,12 @@ def refuse_dirichlet(opts, who):
         raise ValueError("%s: --dirichlet is not supported by the slab decomposition (it passes no view of an array of held cells); run it on one GPU" % who)
 
 
+def refuse_scale(opts, who):
+    """--scale has no slab form: the slab classes pass views of two arrays, none of an array of per-cell factors."""
+    if "--scale" in list(opts or ()):
+        raise ValueError("%s: --scale is not supported by the slab decomposition (it passes no view of an array of per-cell factors); run it on one GPU" % who)
+
+
 def slab_bounds(L, world, rank):
     """Planes [z0, z1) owned by `rank` (balanced split of the outermost dim)."""
     return (rank * L) // world, ((rank + 1) * L) // world
@@ -329,10 +335,12 @@ class HipSweep:
         refuse_second_order(opts, "HipSweep")
         refuse_source(opts, "HipSweep")
         refuse_dirichlet(opts, "HipSweep")
+        refuse_scale(opts, "HipSweep")
         refuse_residual(opts, "HipSweep")
         refuse_second_order(alone_opts, "HipSweep")
         refuse_source(alone_opts, "HipSweep")
         refuse_dirichlet(alone_opts, "HipSweep")
+        refuse_scale(alone_opts, "HipSweep")
         refuse_residual(alone_opts, "HipSweep")
         self.base_stc, self.opts, self.cache_dir = base_stc, list(opts), cache_dir
         self.alone_opts = list(alone_opts) if alone_opts else None
@@ -450,6 +458,7 @@ class SlabRun:
         refuse_second_order(getattr(sweep, "opts", None), "SlabRun")
         refuse_source(getattr(sweep, "opts", None), "SlabRun")
         refuse_dirichlet(getattr(sweep, "opts", None), "SlabRun")
+        refuse_scale(getattr(sweep, "opts", None), "SlabRun")
         refuse_residual(getattr(sweep, "opts", None), "SlabRun")
         self.torch, self.dist = torch, dist
         dims = tuple(dims)
@@ -644,10 +653,12 @@ class NativeSlabRun:
         refuse_second_order(opts, "NativeSlabRun")
         refuse_source(opts, "NativeSlabRun")
         refuse_dirichlet(opts, "NativeSlabRun")
+        refuse_scale(opts, "NativeSlabRun")
         refuse_residual(opts, "NativeSlabRun")
         refuse_second_order(alone_opts, "NativeSlabRun")
         refuse_source(alone_opts, "NativeSlabRun")
         refuse_dirichlet(alone_opts, "NativeSlabRun")
+        refuse_scale(alone_opts, "NativeSlabRun")
         refuse_residual(alone_opts, "NativeSlabRun")
         self.torch, self.dist = torch, dist
         dims = tuple(dims)

@@ -71,6 +71,7 @@ int drs_kernel_unload(drs_kernel *k);
  *   "time_order": 2                only for kernels generated with --time-order 2 (see drs_kernel_launch).
  *   "source": 1                    only for kernels generated with --source (see drs_kernel_launch_src).
  *   "dirichlet": 1                 only for kernels generated with --dirichlet (see drs_kernel_launch_fix).
+ *   "scale": 1, "scale_centre": C  only for kernels generated with --scale (see drs_kernel_launch_ops): C is 0 without a centre term.
  *   "residual": "max", "residual_elems": N   only for kernels generated with --residual max (see drs_kernel_launch_res): N = 1 + "grid". */
 const char *drs_kernel_info(const drs_kernel *k);
 const char *drs_kernel_path(const drs_kernel *k);   /* the loaded shared object */
@@ -207,6 +208,39 @@ int drs_kernel_run_timed_fix(drs_kernel *k, void *d_a, void *d_b, const void *d_
 /* drs_kernel_solve with held cells: the same loop and the same answers (0, 1, -4; -2 also on a kernel without --residual max) */
 int drs_kernel_solve_fix(drs_kernel *k, void *d_a, void *d_b, const void *d_src, void *d_res, const void *d_fix, double tol, int max_launches, int check_every_pairs,
                          void *stream, int *launches, double *residual);
+
+/* ---- the operand block: every array a launch takes beside in and out ------------------------------------------------------------------
+ * No reference counterpart.  One family of entry points for EVERY kernel, old kinds included, instead of one suffixed family per option.
+ * The caller sets size = sizeof(drs_operands) and each pointer the kernel takes, NULL for the others:
+ *   src    --source         read only, the grid's shape and dtype
+ *   res    --residual max   drs_kernel_residual_elems(k) elements, written whole by every launch
+ *   fix    --dirichlet      read only, the grid's shape and dtype
+ *   scale  --scale          read only, the grid's shape and dtype
+ * -2 (the "wrong kind" code of every family): size is not sizeof(drs_operands), a pointer the kernel needs is NULL, or a pointer the kernel
+ * does not take is non-NULL.  The gold kernel computes no residual: the gold forms leave res alone, and accept one only on a --residual
+ * max kernel.  -1 is a HIP error, -3 as drs_kernel_run.
+ * --scale: a kernel generated with --scale is dr_<name>(in, out[, src][, res][, fix], w).  At every interior point p it computes
+ *   v = S(in)[p]  (the unchanged FMA chain);  v = w[p] * v;  with --scale-centre c != 0: t = C * in[p]; v = t + v;
+ * then - out_old[p] (--time-order 2), + src[p] (--source), the --dirichlet select, the residual update and the store, as without the
+ * option.  Every operation is rounded once, nothing is contracted.  C is c as a coefficient is written (six digits, cast to the dtype;
+ * "scale_centre" in drs_kernel_info).  Only the INTERIOR of w is read, each value reaching only its own cell; w is never written, must not
+ * overlap d_out and follows the alignment rule of the other arrays.  Ring fills touch d_in only.  With w = 1 everywhere and no centre
+ * term the stored bits are those of the same command without the option.
+ * Such a plugin exports drs_plugin_launch_ops / drs_plugin_launch_gold_ops INSTEAD of every other launch entry point: every entry point
+ * above (the plain, _src, _res and _fix families and drs_kernel_solve) returns -2 on it; it runs through the five below only.
+ * --step n > 1, --temporal, --gpus N > 1, --pair-launch 1 and the drs_slab_* runtime refuse --scale. */
+typedef struct { size_t size; const void *src; void *res; const void *fix; const void *scale; } drs_operands;
+/* one launch (in -> out), asynchronous on `stream` */
+int drs_kernel_launch_ops(drs_kernel *k, const void *d_in, void *d_out, const drs_operands *ops, void *stream);
+/* gold_<name> with the same operands */
+int drs_kernel_launch_gold_ops(drs_kernel *k, const void *d_in, void *d_out, const drs_operands *ops, void *stream);
+/* the ping-pong loop k(A,B,ops); k(B,A,ops); gold != 0 runs gold_<name>.  Returns the launches made. */
+int drs_kernel_run_ops(drs_kernel *k, void *d_a, void *d_b, const drs_operands *ops, int iterations, int gold, void *stream);
+/* `warmup` launches (A,B), then the loop between two events */
+int drs_kernel_run_timed_ops(drs_kernel *k, void *d_a, void *d_b, const drs_operands *ops, int iterations, int warmup, void *stream, float *ms);
+/* drs_kernel_solve through the operand block (0, 1, -4; -2 also on a kernel without --residual max) */
+int drs_kernel_solve_ops(drs_kernel *k, void *d_a, void *d_b, const drs_operands *ops, double tol, int max_launches, int check_every_pairs, void *stream,
+                         int *launches, double *residual);
 
 /* ---- N > 1: one rank of a slab-decomposed run (z slabs in 3D, y slabs in 2D), one process per GPU -----------------------------
  * No reference counterpart: the reference is single-GPU (no cudaSetDevice / streams / NCCL anywhere; SURVEY.md section 5 sketches

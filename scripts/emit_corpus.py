@@ -255,8 +255,37 @@ def dirichlet_lists():
     return [(None, l) for l in lists] + [(None, j) for j in dirichlet_cases.all_build_args()]       # what build() emits for the dirichlet tests
 
 
+def scale_lists():
+    """--scale and --scale-centre.  Behind everything else, so that the lists in front keep their numbers: against a build without the
+    options `diff -r` shows these files (and --help) and nothing else."""
+    import scale_cases
+    scl3 = ["--3d", "--dtype", "fp32", "--scale", "--check"]
+    cen = ["--scale-centre", "0.3"]
+    lists = [
+        # the emitted main() with the array of factors, every issue point of the scale stream, with and without a centre term, all six
+        # streams at once, the centre stream shared with the residual, the knob bases
+        scl3 + [stc("t3_wave")], scl3 + cen + [stc("t3_wave")], scl3 + ["--store-mask", "buffer", stc("t3_wave")], scl3 + cen + ["--store-mask", "buffer", stc("t3_wave")],
+        scl3 + ["--prefetch", "--prefetch-depth", "2", stc("t3_wave")], scl3 + cen + ["--prefetch", "--prefetch-depth", "2", "--store-mask", "buffer", stc("t3_wave")],
+        scl3 + cen + ["--source", "--time-order", "2", "--residual", "max", "--dirichlet", "--prefetch", "--prefetch-depth", "2", stc("t3_wave")],
+        scl3 + cen + ["--residual", "max", stc("t3_wave")], scl3 + ["--residual", "max", stc("t3_wave")], scl3 + cen + ["--stage", "dma", stc("t3_wave")],
+        scl3 + cen + ["--order", "rows", "--pack", "1", "--block-merge-x", "4", "--defer-stores", "1", "--prefetch", stc("t3_wave")],
+        ["--dtype", "fp64", "--scale", "--scale-centre", "2", "--time-order", "2", "--check", stc("lap2")], ["--dtype", "fp32", "--scale", "--scale-centre", "1", "--boundary", "reflect", stc("lap2")],
+        ["--dtype", "fp64", "--scale", "--scale-centre", "-1.5", "--streaming", "--stage", "dma", stc("t2_star")],
+        # the options have one place in the banner; the centre as a coefficient is written; 0 leaves no trace
+        ["--scale", "--3d", "--scale-centre", "0.30000001", "--scale", "--dtype", "fp32", stc("t3_wave")], ["--scale-centre", "0", "--3d", "--scale", "--dtype", "fp32", stc("t3_wave")],
+        # rejected before the emitter is asked
+        ["--3d", "--scale", "--step", "2", stc("t3_star")], ["--3d", "--scale", "--step", "2", "--temporal", "1", stc("t3_star")],
+        ["--3d", "--scale", "--temporal", "force", stc("t3_star")], ["--3d", "--scale", "--gpus", "2", stc("t3_star")],
+        ["--3d", "--scale", "--pair-launch", "1", stc("t3_star")], ["--3d", "--scale-centre", "1", stc("t3_star")], ["--3d", "--scale", "--scale-centre", "nan", stc("t3_star")],
+    ]
+    for b in ("d3", "d3f64", "rows", "tile", "cross", "stream", "odd"):
+        opts, name = BASES[b]
+        lists.append(list(opts) + ["--scale", "--scale-centre", "1", stc(name)])
+    return [(None, l) for l in lists] + [(None, j) for j in scale_cases.all_build_args()]       # what build() emits for the scale tests
+
+
 def corpus():
-    return build_lists() + space_sample() + host_lists() + knob_lists() + boundary_lists() + source_lists() + residual_lists() + dirichlet_lists()
+    return build_lists() + space_sample() + host_lists() + knob_lists() + boundary_lists() + source_lists() + residual_lists() + dirichlet_lists() + scale_lists()
 
 
 def coverage(lists):
