@@ -21,7 +21,8 @@ _lib = None
 
 class Operands(ctypes.Structure):
     """drs_operands of include/drstencil_amd.h: every array a launch takes beside in and out (device addresses; None where the kernel takes none)."""
-    _fields_ = [("size", ctypes.c_size_t), ("src", ctypes.c_void_p), ("res", ctypes.c_void_p), ("fix", ctypes.c_void_p), ("scale", ctypes.c_void_p)]
+    _fields_ = [("size", ctypes.c_size_t), ("src", ctypes.c_void_p), ("res", ctypes.c_void_p), ("fix", ctypes.c_void_p), ("scale", ctypes.c_void_p),
+                ("coef", ctypes.c_void_p)]
 
 
 class NativeLibraryMissing(RuntimeError):
@@ -89,6 +90,8 @@ def lib():
     L.drs_kernel_run_ops.argtypes = [vp, vp, vp, op, ci, ci, vp]
     L.drs_kernel_run_timed_ops.argtypes = [vp, vp, vp, op, ci, ci, vp, ctypes.POINTER(ctypes.c_float)]
     L.drs_kernel_solve_ops.argtypes = [vp, vp, vp, op, ctypes.c_double, ci, ci, vp, ctypes.POINTER(ci), ctypes.POINTER(ctypes.c_double)]
+    L.drs_kernel_coef_taps.argtypes = [vp]
+    L.drs_kernel_coef_taps.restype = ctypes.c_char_p
     L.drs_kernel_residual.argtypes = [vp, vp, ctypes.POINTER(ctypes.c_double)]
     L.drs_kernel_solve.argtypes = [vp, vp, vp, vp, vp, ctypes.c_double, ci, ci, vp, ctypes.POINTER(ci), ctypes.POINTER(ctypes.c_double)]
     L.drs_slab_unique_id.argtypes = [vp]
@@ -125,6 +128,7 @@ EXPORTS = [
     "drs_kernel_residual_elems", "drs_kernel_launch_res", "drs_kernel_run_res", "drs_kernel_run_timed_res", "drs_kernel_residual", "drs_kernel_solve",
     "drs_kernel_launch_fix", "drs_kernel_launch_gold_fix", "drs_kernel_run_fix", "drs_kernel_run_timed_fix", "drs_kernel_solve_fix",
     "drs_kernel_launch_ops", "drs_kernel_launch_gold_ops", "drs_kernel_run_ops", "drs_kernel_run_timed_ops", "drs_kernel_solve_ops",
+    "drs_kernel_coef_taps",
     "drs_fill_random_f64", "drs_fill_random_f32", "drs_check_error_f64", "drs_check_error_f32",
     "drs_slab_unique_id", "drs_slab_open", "drs_slab_plan", "drs_slab_connect", "drs_slab_run", "drs_slab_sync", "drs_slab_stream", "drs_slab_info",
     "drs_slab_error", "drs_slab_close",
@@ -272,10 +276,35 @@ class Kernel:
             raise ValueError("%s(): d_scale given, but the kernel was generated without --scale" % who)
         return d_scale
 
-    def _ops(self, who, d_src, d_res, d_fix, d_scale, gold=False):
+    def _coef(self, d_coef, who):
+        """The coefficient grids of a call, checked against the kernel: a --varcoef kernel needs them, any other kernel takes none."""
+        if self.varcoef and not d_coef:
+            raise ValueError("%s(): the kernel was generated with --varcoef and needs d_coef, the array of per-tap coefficients, shape (%d,) + grid" % (who, len(self.coef_taps)))
+        if not self.varcoef and d_coef is not None:
+            raise ValueError("%s(): d_coef given, but the kernel was generated without --varcoef" % who)
+        return d_coef
+
+    def _ops(self, who, d_src, d_res, d_fix, d_scale, gold=False, d_coef=None):
         """The operand block (drs_operands) of a call, every array checked against the kernel (the gold kernel computes no residual)."""
         return ctypes.byref(Operands(ctypes.sizeof(Operands), self._src(d_src, who), None if gold else self._res(d_res, who), self._fix(d_fix, who),
-                                     self._scale(d_scale, who)))
+                                     self._scale(d_scale, who), self._coef(d_coef, who)))
+
+    def _by_ops(self, d_scale, d_coef, who):
+        """True when the call goes through the operand-block entry points: --scale and --varcoef kernels run through them only."""
+        return bool(self._scale(d_scale, who)) | bool(self._coef(d_coef, who))
+
+    @property
+    def varcoef(self):
+        """True for kernels generated with --varcoef: a launch takes one more read-only array d_coef of the grid's dtype and shape
+        (T,) + grid, T = len(coef_taps), and computes v = sum_t coef[t][p] * in[p + d_t] as the kernel's FMA chain, the array value in the
+        constant's place, in front of every other option's operation.  launch, launch_gold, run, run_timed and solve then need the keyword
+        d_coef, the same array for every launch of a loop; such a kernel runs through the operand-block entry points (drs_kernel_*_ops)."""
+        return bool(self.info.get("varcoef", 0))
+
+    @property
+    def coef_taps(self):
+        """The taps of a --varcoef kernel as (k, j, i) offsets, in the order of d_coef's grids (k = 0 in 2D); () for any other kernel."""
+        return tuple(tuple(t) for t in self.info.get("coef_taps", ()))
 
     @property
     def scale(self):
@@ -313,14 +342,14 @@ class Kernel:
             raise RuntimeError("HIP error reading the residual")
         return float(v.value)
 
-    def solve(self, d_a, d_b, d_res, tol, max_launches, check_every=8, d_src=None, stream=0, d_fix=None, d_scale=None):
+    def solve(self, d_a, d_b, d_res, tol, max_launches, check_every=8, d_src=None, stream=0, d_fix=None, d_scale=None, d_coef=None):
         """Run to tolerance (drs_kernel_solve): ping-pong pairs k(A,B); k(B,A), `check_every` pairs between two looks at the residual, until
         it is <= tol.  (status, launches, residual): status 0 converged, 1 max_launches (rounded down to an even number) reached, -4 the
         residual is NaN or inf (a diverged or overflowed run).  The answer is in A.  --dirichlet kernels: d_fix, the held cells (drs_kernel_solve_fix)."""
         self._res(d_res, "solve")
         n, r = ctypes.c_int(), ctypes.c_double()
-        if self._scale(d_scale, "solve"):
-            rc = lib().drs_kernel_solve_ops(self.h, d_a, d_b, self._ops("solve", d_src, d_res, d_fix, d_scale), tol, max_launches, check_every, stream, ctypes.byref(n), ctypes.byref(r))
+        if self._by_ops(d_scale, d_coef, "solve"):
+            rc = lib().drs_kernel_solve_ops(self.h, d_a, d_b, self._ops("solve", d_src, d_res, d_fix, d_scale, d_coef=d_coef), tol, max_launches, check_every, stream, ctypes.byref(n), ctypes.byref(r))
         elif self._fix(d_fix, "solve"):
             rc = lib().drs_kernel_solve_fix(self.h, d_a, d_b, self._src(d_src, "solve"), d_res, d_fix, tol, max_launches, check_every, stream, ctypes.byref(n), ctypes.byref(r))
         else:
@@ -331,9 +360,9 @@ class Kernel:
             raise RuntimeError("HIP error in drs_kernel_solve")
         return rc, n.value, r.value
 
-    def launch(self, d_in, d_out, stream=0, d_src=None, d_res=None, d_fix=None, d_scale=None):
-        if self._scale(d_scale, "launch"):
-            rc = lib().drs_kernel_launch_ops(self.h, d_in, d_out, self._ops("launch", d_src, d_res, d_fix, d_scale), stream)
+    def launch(self, d_in, d_out, stream=0, d_src=None, d_res=None, d_fix=None, d_scale=None, d_coef=None):
+        if self._by_ops(d_scale, d_coef, "launch"):
+            rc = lib().drs_kernel_launch_ops(self.h, d_in, d_out, self._ops("launch", d_src, d_res, d_fix, d_scale, d_coef=d_coef), stream)
         elif self._fix(d_fix, "launch"):
             rc = lib().drs_kernel_launch_fix(self.h, d_in, d_out, self._src(d_src, "launch"), self._res(d_res, "launch"), d_fix, stream)
         elif self._res(d_res, "launch"):
@@ -394,9 +423,9 @@ class Kernel:
         if rc != 0:
             raise RuntimeError("HIP launch error %d" % rc)
 
-    def launch_gold(self, d_in, d_out, stream=0, d_src=None, d_fix=None, d_scale=None):
-        if self._scale(d_scale, "launch_gold"):
-            rc = lib().drs_kernel_launch_gold_ops(self.h, d_in, d_out, self._ops("launch_gold", d_src, None, d_fix, d_scale, gold=True), stream)
+    def launch_gold(self, d_in, d_out, stream=0, d_src=None, d_fix=None, d_scale=None, d_coef=None):
+        if self._by_ops(d_scale, d_coef, "launch_gold"):
+            rc = lib().drs_kernel_launch_gold_ops(self.h, d_in, d_out, self._ops("launch_gold", d_src, None, d_fix, d_scale, gold=True, d_coef=d_coef), stream)
         elif self._fix(d_fix, "launch_gold"):
             rc = lib().drs_kernel_launch_gold_fix(self.h, d_in, d_out, self._src(d_src, "launch_gold"), d_fix, stream)
         elif self._src(d_src, "launch_gold"):
@@ -406,15 +435,15 @@ class Kernel:
         if rc != 0:
             raise RuntimeError("HIP launch error %d" % rc)
 
-    def run(self, d_a, d_b, iterations=None, gold=False, stream=0, d_src=None, d_res=None, d_fix=None, d_scale=None):
+    def run(self, d_a, d_b, iterations=None, gold=False, stream=0, d_src=None, d_res=None, d_fix=None, d_scale=None, d_coef=None):
         """The reference's ping-pong loop (codegen.hpp:581-584); result ends in A.  --source kernels: the same d_src in every launch.
         --residual kernels: d_res[0] then holds the last launch's residual (the gold kernel computes none: gold=True takes no d_res)."""
         it = self.info["iterations"] if iterations is None else iterations
         self._fix(d_fix, "run")
-        if self._scale(d_scale, "run"):
+        if self._by_ops(d_scale, d_coef, "run"):
             if gold and d_res is not None:
                 raise ValueError("run(): the gold kernel computes no residual")
-            n = lib().drs_kernel_run_ops(self.h, d_a, d_b, self._ops("run", d_src, d_res, d_fix, d_scale, gold=gold), it, 1 if gold else 0, stream)
+            n = lib().drs_kernel_run_ops(self.h, d_a, d_b, self._ops("run", d_src, d_res, d_fix, d_scale, gold=gold, d_coef=d_coef), it, 1 if gold else 0, stream)
         elif gold and self.residual_elems:
             # gold_<name> keeps its entry point: the loop is made of single launches
             if d_res is not None:
@@ -461,12 +490,12 @@ class Kernel:
             out.append(("top", dim0 - nsl))
         return out
 
-    def run_timed(self, d_a, d_b, iterations=None, warmup=10, stream=0, d_src=None, d_res=None, d_fix=None, d_scale=None):
+    def run_timed(self, d_a, d_b, iterations=None, warmup=10, stream=0, d_src=None, d_res=None, d_fix=None, d_scale=None, d_coef=None):
         """Warm-up launches + timed loop bracketed by HIP events on `stream`: (launches, ms)."""
         it = self.info["iterations"] if iterations is None else iterations
         ms = ctypes.c_float()
-        if self._scale(d_scale, "run_timed"):
-            n = lib().drs_kernel_run_timed_ops(self.h, d_a, d_b, self._ops("run_timed", d_src, d_res, d_fix, d_scale), it, warmup, stream, ctypes.byref(ms))
+        if self._by_ops(d_scale, d_coef, "run_timed"):
+            n = lib().drs_kernel_run_timed_ops(self.h, d_a, d_b, self._ops("run_timed", d_src, d_res, d_fix, d_scale, d_coef=d_coef), it, warmup, stream, ctypes.byref(ms))
         elif self._fix(d_fix, "run_timed"):
             n = lib().drs_kernel_run_timed_fix(self.h, d_a, d_b, self._src(d_src, "run_timed"), self._res(d_res, "run_timed"), d_fix, it, warmup, stream, ctypes.byref(ms))
         elif self._res(d_res, "run_timed"):
@@ -502,7 +531,8 @@ class Kernel:
         # values of --residual are cells the sweep reads anyway)
         # --dirichlet reads the array of held cells: one more whole array
         # --scale reads the array of factors: one more whole array (the centre values of --scale-centre are cached re-reads, as --residual's)
-        return (2 + (self.time_order == 2) + self.source + self.dirichlet + self.scale) * (4 if i["dtype"] == "fp32" else 8) * pts
+        # --varcoef reads the T coefficient grids: T more whole arrays
+        return (2 + (self.time_order == 2) + self.source + self.dirichlet + self.scale + len(self.coef_taps)) * (4 if i["dtype"] == "fp32" else 8) * pts
 
     # ---- placement of the output array (csrc/schedule.hpp: Schedule::out_skew_bytes; profiles/r03_probe_skew4.log) ----
     def array_bytes(self):

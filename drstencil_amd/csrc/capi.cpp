@@ -45,6 +45,11 @@ struct drs_kernel {
     // --scale kernels: these two, with every array in their signatures (null where the option is off), INSTEAD of all the others
     int (*launch_ops)(const void *, void *, const void *, void *, const void *, const void *, hipStream_t) = nullptr;
     int (*launch_gold_ops)(const void *, void *, const void *, const void *, const void *, hipStream_t) = nullptr;
+    // --varcoef kernels: the same two names with ONE MORE pointer (coef, behind scale); which signature a plugin has is known from the plan
+    int (*launch_opsk)(const void *, void *, const void *, void *, const void *, const void *, const void *, hipStream_t) = nullptr;
+    int (*launch_gold_opsk)(const void *, void *, const void *, const void *, const void *, const void *, hipStream_t) = nullptr;
+    bool has_coef = false;
+    std::string coef_taps;       // "[[k,j,i],...]" of a --varcoef kernel, else empty
     long residual_elems = 0;     // elements of d_res (1 + launched workgroups); 0: no --residual
     bool has_source = false, has_fix = false, has_scale = false, fp32 = false;
     int (*wrap)(void *, hipStream_t) = nullptr;              // only with a non-fixed boundary (--boundary periodic / reflect, --boundary-x / -y / -z)
@@ -362,6 +367,16 @@ drs_kernel *drs_kernel_build(int argc, const char *const *argv, const char *cach
     k->has_source = r.plan.source;
     k->has_fix = r.plan.dirichlet;
     k->has_scale = r.plan.scale;
+    k->has_coef = r.plan.varcoef;
+    if (k->has_coef) {
+        k->launch_opsk = (decltype(k->launch_opsk))(void *)k->launch_ops;
+        k->launch_gold_opsk = (decltype(k->launch_gold_opsk))(void *)k->launch_gold_ops;
+        for (auto &t : r.plan.taps) {
+            const int kk = r.plan.ndim == 3 ? t.ds : 0, jj = r.plan.ndim == 3 ? t.dy : r.plan.has_y ? t.dy : t.ds;
+            k->coef_taps += (k->coef_taps.empty() ? "[[" : ",[") + std::to_string(kk) + "," + std::to_string(jj) + "," + std::to_string(t.dx) + "]";
+        }
+        k->coef_taps += "]";
+    }
     k->fp32 = r.plan.fp32;
     k->residual_elems = r.plan.residual ? Schedule(r.plan, r.opt).residual_elems() : 0;
     k->wrap = (int (*)(void *, hipStream_t))dlsym(dl, "drs_plugin_wrap");
@@ -383,8 +398,8 @@ drs_kernel *drs_kernel_build(int argc, const char *const *argv, const char *cach
     const bool with_fix = k->launch_fix && k->launch_gold_fix && !others;
     // --scale: its two entry points and none of the others, --dirichlet's included
     const bool with_ops = k->launch_ops && k->launch_gold_ops && !others && !k->launch_fix && !k->launch_gold_fix;
-    const bool fix_ok = r.plan.scale ? with_ops : (!k->launch_ops && !k->launch_gold_ops && (r.plan.dirichlet ? with_fix : (!k->launch_fix && !k->launch_gold_fix)));
-    if (!fix_ok || (!r.plan.dirichlet && !r.plan.scale && (!(plain || with_src) || with_src != r.plan.source)) || !k->info) {
+    const bool fix_ok = (r.plan.scale || r.plan.varcoef) ? with_ops : (!k->launch_ops && !k->launch_gold_ops && (r.plan.dirichlet ? with_fix : (!k->launch_fix && !k->launch_gold_fix)));
+    if (!fix_ok || (!r.plan.dirichlet && !r.plan.scale && !r.plan.varcoef && (!(plain || with_src) || with_src != r.plan.source)) || !k->info) {
         if (log) *log = dup_cstr("plugin " + so + " lacks the drs_plugin_* entry points\n");
         dlclose(dl);
         delete k;
@@ -672,16 +687,17 @@ int drs_kernel_solve_fix(drs_kernel *k, void *d_a, void *d_b, const void *d_src,
 // ops->size is checked; a pointer the kernel needs must be non-null and a pointer it does not take must be null, else -2 (the gold kernel
 // computes no residual: the gold forms leave ops->res alone, and take it only on a --residual max kernel)
 namespace {
-struct Operands { const void *src = nullptr; void *res = nullptr; const void *fix = nullptr; const void *scale = nullptr; };
+struct Operands { const void *src = nullptr; void *res = nullptr; const void *fix = nullptr; const void *scale = nullptr; const void *coef = nullptr; };
 bool ops_ok(const drs_kernel *k, const drs_operands *ops, bool gold, Operands &v) {
     if (!k || !ops || ops->size != sizeof(drs_operands)) return false;
-    v.src = ops->src; v.res = ops->res; v.fix = ops->fix; v.scale = ops->scale;
-    if ((v.src != nullptr) != k->has_source || (v.fix != nullptr) != k->has_fix || (v.scale != nullptr) != k->has_scale) return false;
+    v.src = ops->src; v.res = ops->res; v.fix = ops->fix; v.scale = ops->scale; v.coef = ops->coef;
+    if ((v.src != nullptr) != k->has_source || (v.fix != nullptr) != k->has_fix || (v.scale != nullptr) != k->has_scale || (v.coef != nullptr) != k->has_coef) return false;
     if (gold) return k->residual_elems ? true : v.res == nullptr;
     return (v.res != nullptr) == (k->residual_elems != 0);
 }
 // one launch through whichever entry points the plugin exports
 int ops_one(drs_kernel *k, const void *in, void *out, const Operands &v, bool gold, hipStream_t s) {
+    if (k->has_coef) return gold ? k->launch_gold_opsk(in, out, v.src, v.fix, v.scale, v.coef, s) : k->launch_opsk(in, out, v.src, v.res, v.fix, v.scale, v.coef, s);
     if (k->has_scale) return gold ? k->launch_gold_ops(in, out, v.src, v.fix, v.scale, s) : k->launch_ops(in, out, v.src, v.res, v.fix, v.scale, s);
     if (k->has_fix) return gold ? k->launch_gold_fix(in, out, v.src, v.fix, s) : k->launch_fix(in, out, v.src, v.res, v.fix, s);
     if (gold) return v.src ? k->launch_gold_src(in, out, v.src, s) : k->launch_gold(in, out, s);
@@ -699,6 +715,7 @@ int ops_loop(drs_kernel *k, void *d_a, void *d_b, const Operands &v, int iterati
     return n;
 }
 }  // namespace
+const char *drs_kernel_coef_taps(const drs_kernel *k) { return (k && k->has_coef) ? k->coef_taps.c_str() : nullptr; }
 int drs_kernel_launch_ops(drs_kernel *k, const void *d_in, void *d_out, const drs_operands *ops, void *stream) {
     Operands v;
     if (!ops_ok(k, ops, false, v)) return -2;

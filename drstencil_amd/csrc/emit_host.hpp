@@ -26,7 +26,7 @@ inline std::string check_call(const KernelPlan &p, const std::string &outer) {
 inline std::string gold_kernel(const KernelPlan &p) {
     std::ostringstream g;
     g << "// naive reference kernel: the verification arithmetic (same term order, same FMA chain)\n";
-    g << "extern \"C\" __global__ void gold_" << p.name << " (const real_t* __restrict__ d_in, real_t* __restrict__ d_out" << (p.source ? ", const real_t* __restrict__ d_src" : "") << (p.dirichlet ? ", const real_t* __restrict__ d_fix" : "") << (p.scale ? ", const real_t* __restrict__ d_scale" : "") << ")\n{\n";
+    g << "extern \"C\" __global__ void gold_" << p.name << " (const real_t* __restrict__ d_in, real_t* __restrict__ d_out" << (p.source ? ", const real_t* __restrict__ d_src" : "") << (p.dirichlet ? ", const real_t* __restrict__ d_fix" : "") << (p.scale ? ", const real_t* __restrict__ d_scale" : "") << (p.varcoef ? ", const real_t* __restrict__ d_coef" : "") << ")\n{\n";
     g << "    const int i = (int)(blockIdx.x * blockDim.x + threadIdx.x);\n";
     g << "    const int j = (int)(blockIdx.y * blockDim.y + threadIdx.y);\n";
     if (p.ndim == 3) g << "    const int k = (int)(blockIdx.z * blockDim.z + threadIdx.z);\n";
@@ -35,17 +35,22 @@ inline std::string gold_kernel(const KernelPlan &p) {
     g << "    if (" << guard << ") {\n";
     g << "        const real_t* c = d_in + " << (p.ndim == 3 ? "((long)k * M + j) * N + i" : "(long)j * N + i") << ";\n";
     bool first = true;
+    const std::string gidx = p.ndim == 3 ? "((long)k * M + j) * N + i" : "(long)j * N + i";
+    // --varcoef: tap t's coefficient is the value of grid t at this cell, in the constant's place
+    if (p.varcoef) g << "        const real_t* a = d_coef + " << gidx << ";\n";
+    int tap = 0;
     // taps are stored in role order; recover (k,j,i) offsets
     for (auto &t : p.gtaps) {
         long off;
         if (p.ndim == 3) off = ((long)t.ds * p.M + t.dy) * p.N + t.dx;
         else if (p.has_y) off = (long)t.dy * p.N + t.dx;
         else off = (long)t.ds * p.N + t.dx;
-        if (first) g << "        real_t t = (real_t)(" << t.coef << ") * c[" << off << "L];\n";
-        else g << "        t = " << (p.fp32 ? "__builtin_fmaf" : "__builtin_fma") << "((real_t)(" << t.coef << "), c[" << off << "L], t);\n";
+        const std::string cf = p.varcoef ? "a[" + std::to_string(tap) + "L * DRS_COEF_GRID]" : "(real_t)(" + t.coef + ")";
+        if (first) g << "        real_t t = " << cf << " * c[" << off << "L];\n";
+        else g << "        t = " << (p.fp32 ? "__builtin_fmaf" : "__builtin_fma") << "(" << cf << ", c[" << off << "L], t);\n";
         first = false;
+        tap++;
     }
-    const std::string gidx = p.ndim == 3 ? "((long)k * M + j) * N + i" : "(long)j * N + i";
     if (p.scale) {       // explicit statements, in the sweep's order, each a rounded operation of its own: w *, [C * in +,] [- old,] [+ src,] [select]
         g << "        t = d_scale[" << gidx << "] * t;\n";
         if (p.centre_term()) g << "        { const real_t u = (real_t)(" << p.scale_centre << ") * c[0]; t = u + t; }\n";
@@ -178,6 +183,15 @@ inline std::string info_json(const Schedule &s) {
     if (p.source) j.insert(j.size() - 1, ",\\\"source\\\":1");
     if (p.dirichlet) j.insert(j.size() - 1, ",\\\"dirichlet\\\":1");
     if (p.scale) j.insert(j.size() - 1, sfmt(",\\\"scale\\\":1,\\\"scale_centre\\\":%s", p.centre_term() ? p.scale_centre.c_str() : "0"));
+    if (p.varcoef) {
+        // tap t of coef, as (k, j, i) offsets (k = 0 in 2D): the order of the gold sum
+        std::string taps;
+        for (auto &t : p.taps) {
+            const int kk = p.ndim == 3 ? t.ds : 0, jj = p.ndim == 3 ? t.dy : p.has_y ? t.dy : t.ds;
+            taps += sfmt("%s[%d,%d,%d]", taps.empty() ? "" : ",", kk, jj, t.dx);
+        }
+        j.insert(j.size() - 1, ",\\\"varcoef\\\":1,\\\"coef_taps\\\":[" + taps + "]");
+    }
     if (p.residual) j.insert(j.size() - 1, sfmt(",\\\"residual\\\":\\\"max\\\",\\\"residual_elems\\\":%ld", s.residual_elems()));
     if (p.periodic) {
         const int H = p.halo;
@@ -205,23 +219,27 @@ inline std::string plugin_api(const Schedule &s) {
     const std::string wrap_in = p.fills_ring() ? "    if (int rc = drs_plugin_wrap((void*)in, stream)) return rc;\n" : "";
     // --source kernels take three arrays: they export the _src entry points INSTEAD of the two-pointer ones
     const std::string sfx = p.source ? "_src" : "", src_par = p.source ? ", const void* src" : "", src_arg = p.source ? ", (const real_t*)src" : "";
-    if (p.scale) {
+    if (p.scale || p.varcoef) {
         // --scale kernels export these two INSTEAD of every other launch entry point, with every array in their signatures: src is null unless
-        // --source, res unless --residual max, fix unless --dirichlet
+        // --source, res unless --residual max, fix unless --dirichlet.  --varcoef kernels export them with ONE MORE pointer, coef, behind
+        // scale (which is null unless --scale): the runtime knows from the plan which of the two signatures a plugin has
         const std::string res_arg = p.residual ? ", (real_t*)res" : "", fix_arg = p.dirichlet ? ", (const real_t*)fix" : "";
-        a << "extern \"C\" int drs_plugin_launch_ops(const void* in, void* out, const void* src, void* res, const void* fix, const void* scale, hipStream_t stream)\n{\n" << wrap_in;
+        const std::string scl_arg = p.scale ? ", (const real_t*)scale" : "", coef_par = p.varcoef ? ", const void* coef" : "", coef_arg = p.varcoef ? ", (const real_t*)coef" : "";
+        a << "extern \"C\" int drs_plugin_launch_ops(const void* in, void* out, const void* src, void* res, const void* fix, const void* scale" << coef_par << ", hipStream_t stream)\n{\n" << wrap_in;
         if (!p.source) a << "    (void)src;\n";
         if (!p.residual) a << "    (void)res;\n";
         if (!p.dirichlet) a << "    (void)fix;\n";
-        a << "    hipLaunchKernelGGL(dr_" << p.name << ", dim3(DRS_GRID), dim3(DRS_NTL), 0, stream, (const real_t*)in, (real_t*)out" << src_arg << res_arg << fix_arg << ", (const real_t*)scale);\n";
+        if (!p.scale) a << "    (void)scale;\n";
+        a << "    hipLaunchKernelGGL(dr_" << p.name << ", dim3(DRS_GRID), dim3(DRS_NTL), 0, stream, (const real_t*)in, (real_t*)out" << src_arg << res_arg << fix_arg << scl_arg << coef_arg << ");\n";
         if (p.residual) a << "    hipLaunchKernelGGL(res_" << p.name << ", dim3(1), dim3(256), 0, stream, (real_t*)res);\n";
         a << "    return (int)hipGetLastError();\n}\n";
-        a << "extern \"C\" int drs_plugin_launch_gold_ops(const void* in, void* out, const void* src, const void* fix, const void* scale, hipStream_t stream)\n{\n" << wrap_in;
+        a << "extern \"C\" int drs_plugin_launch_gold_ops(const void* in, void* out, const void* src, const void* fix, const void* scale" << coef_par << ", hipStream_t stream)\n{\n" << wrap_in;
         if (!p.source) a << "    (void)src;\n";
         if (!p.dirichlet) a << "    (void)fix;\n";
+        if (!p.scale) a << "    (void)scale;\n";
         if (p.ndim == 3) a << "    dim3 b(64, 2, 2), g((N + 63) / 64, (M + 1) / 2, (L + 1) / 2);\n";
         else a << "    dim3 b(64, 4, 1), g((N + 63) / 64, (M + 3) / 4, 1);\n";
-        a << "    hipLaunchKernelGGL(gold_" << p.name << ", g, b, 0, stream, (const real_t*)in, (real_t*)out" << src_arg << fix_arg << ", (const real_t*)scale);\n";
+        a << "    hipLaunchKernelGGL(gold_" << p.name << ", g, b, 0, stream, (const real_t*)in, (real_t*)out" << src_arg << fix_arg << scl_arg << coef_arg << ");\n";
         a << "    return (int)hipGetLastError();\n}\n";
         a << "extern \"C\" const char* drs_plugin_info(void)\n{\n    return \"" << info_json(s) << "\";\n}\n\n";
         return a.str();
@@ -659,11 +677,13 @@ inline std::string host_main(const Schedule &s) {
     if (p.second_order) h << "    real_t* h_in = getRandomArray<real_t> (npoints);\n    real_t* h_out = getRandomArray<real_t> (npoints);   // time order 2: out holds u(t-1), input too (the rand() sequence continued)\n";
     else h << "    real_t* h_in = getRandomArray<real_t> (npoints);\n    real_t* h_out = getZeroArray<real_t> (npoints);\n";
     // --source: the third array continues the reference's rand() fill behind the arrays filled today; it lies behind the pair in the same arena
-    const std::string launch = p.scale ? "drs_plugin_launch_ops" : p.dirichlet ? "drs_plugin_launch_fix" : p.residual ? "drs_plugin_launch_res" : p.source ? "drs_plugin_launch_src" : "drs_plugin_launch",
-                      gold = p.scale ? "drs_plugin_launch_gold_ops" : p.dirichlet ? "drs_plugin_launch_gold_fix" : p.source ? "drs_plugin_launch_gold_src" : "drs_plugin_launch_gold";
+    const bool ops = p.scale || p.varcoef;
+    const std::string launch = ops ? "drs_plugin_launch_ops" : p.dirichlet ? "drs_plugin_launch_fix" : p.residual ? "drs_plugin_launch_res" : p.source ? "drs_plugin_launch_src" : "drs_plugin_launch",
+                      gold = ops ? "drs_plugin_launch_gold_ops" : p.dirichlet ? "drs_plugin_launch_gold_fix" : p.source ? "drs_plugin_launch_gold_src" : "drs_plugin_launch_gold";
     // --dirichlet and --scale: every array in both signatures, NULL where its option is off
-    const std::string gsarg = p.scale ? std::string(p.source ? ", src" : ", NULL") + (p.dirichlet ? ", d_fix" : ", NULL") + ", d_scale" : p.dirichlet ? std::string(p.source ? ", src" : ", NULL") + ", d_fix" : p.source ? ", src" : "";       // the gold kernel computes no residual
-    const std::string sarg = p.scale ? std::string(p.source ? ", src" : ", NULL") + (p.residual ? ", d_res" : ", NULL") + (p.dirichlet ? ", d_fix" : ", NULL") + ", d_scale"
+    const std::string tail = std::string(p.scale ? ", d_scale" : ", NULL") + (p.varcoef ? ", d_coef" : "");
+    const std::string gsarg = ops ? std::string(p.source ? ", src" : ", NULL") + (p.dirichlet ? ", d_fix" : ", NULL") + tail : p.dirichlet ? std::string(p.source ? ", src" : ", NULL") + ", d_fix" : p.source ? ", src" : "";       // the gold kernel computes no residual
+    const std::string sarg = ops ? std::string(p.source ? ", src" : ", NULL") + (p.residual ? ", d_res" : ", NULL") + (p.dirichlet ? ", d_fix" : ", NULL") + tail
                            : p.dirichlet ? std::string(p.source ? ", src" : ", NULL") + (p.residual ? ", d_res" : ", NULL") + ", d_fix"
                                          : p.residual ? (p.source ? ", src, d_res" : ", NULL, d_res") : gsarg;
     if (p.source) h << "    real_t* h_src = getRandomArray<real_t> (npoints);   // the source term (the rand() sequence continued)\n";
@@ -693,6 +713,14 @@ inline std::string host_main(const Schedule &s) {
              "    for (size_t x = 0; x < npoints; x++) h_scale[x] = (real_t)0.5 + (real_t)0.5 * h_scale[x];\n"
              "    real_t *d_scale;\n    (void)hipMalloc (&d_scale, nbytes);\n    check_error (\"Failed to allocate device memory for scale.\\n\");\n"
              "    (void)hipMemcpy (d_scale, h_scale, nbytes, hipMemcpyHostToDevice);\n";
+    if (p.varcoef)
+        // the coefficient grids continue the rand() fill behind every other array, mapped into [0.5, 1) / T: the magnitudes of a cell's T
+        // coefficients sum to less than 1, so iterating stays finite.  An allocation of its own, so that the other arrays' places stay as they are
+        h << "    const size_t ncoef = " << p.taps.size() << "UL * npoints;   // --varcoef: " << p.taps.size() << " grids, tap t's at t * npoints\n"
+             "    real_t* h_coef = getRandomArray<real_t> (ncoef);   // (the rand() sequence continued): coefficients in [0.5, 1) / " << p.taps.size() << "\n"
+             "    for (size_t x = 0; x < ncoef; x++) h_coef[x] = ((real_t)0.5 + (real_t)0.5 * h_coef[x]) / (real_t)" << p.taps.size() << ";\n"
+             "    real_t *d_coef;\n    (void)hipMalloc (&d_coef, sizeof(real_t) * ncoef);\n    check_error (\"Failed to allocate device memory for coef.\\n\");\n"
+             "    (void)hipMemcpy (d_coef, h_coef, sizeof(real_t) * ncoef, hipMemcpyHostToDevice);\n";
     if (p.residual) h << "    real_t *d_res;   // --residual: [0] the last launch's max |out - in|, then one partial per workgroup; written whole by every launch\n"
                          "    (void)hipMalloc (&d_res, sizeof(real_t) * DRS_RES_ELEMS);\n    check_error (\"Failed to allocate device memory for the residual.\\n\");\n";
     h << "    puts(\"GPU computing ...\");\n\n    // warm up\n    for (int i = 0; i < 10; i ++) " << launch << " (in, out" << sarg << ", 0);\n\n";
@@ -704,7 +732,7 @@ inline std::string host_main(const Schedule &s) {
     h << "    (void)hipEventRecord (ev1, 0);\n    (void)hipDeviceSynchronize();\n    check_error (\"Kernel error\");\n    float ms = 0.f;\n    (void)hipEventElapsedTime (&ms, ev0, ev1);\n";
     h << "    puts(\"GPU finished computing.\");\n    printf(\"GPU computation time: %f ms\\n\", ms);\n";
     h << "    {\n        const double updates = (double)launches * Step * " << interior_expr(p) << ";\n"
-         "        const double bytes = (double)launches * " << sfmt("%d.0", 2 + s.extra_streams()) << " * sizeof(real_t) * (double)npoints;\n"
+         "        const double bytes = (double)launches * " << sfmt("%d.0", 2 + s.extra_streams() + (p.varcoef ? (int)p.taps.size() : 0)) << " * sizeof(real_t) * (double)npoints;\n"
          "        if (launches > 0 && ms > 0.f) {\n"
          "            printf(\"[Perf] %.3f GStencil/s, %d launches\\n\", updates / (ms * 1e-3) / 1e9, launches);\n"
          "            printf(\"[Perf] achieved %.1f GB/s = %.1f %% of the MI355X HBM3E roofline (8000 GB/s)\\n\", bytes / (ms * 1e-3) / 1e9, bytes / (ms * 1e-3) / 8e12 * 100.0);\n"
@@ -742,6 +770,7 @@ inline std::string host_main(const Schedule &s) {
     if (p.residual) h << "\n    (void)hipFree (d_res);";
     if (p.dirichlet) h << "\n    delete[] h_fix;\n    (void)hipFree (d_fix);";
     if (p.scale) h << "\n    delete[] h_scale;\n    (void)hipFree (d_scale);";
+    if (p.varcoef) h << "\n    delete[] h_coef;\n    (void)hipFree (d_coef);";
     h << "\n    delete[] h_in;\n    delete[] h_out;\n    (void)hipFree (arena);\n    return 0;\n}\n#endif\n";
     return h.str();
 }

@@ -167,6 +167,20 @@ MI355X options:
                           heterogeneous diffusion  u' = u + k*L(u)            --scale --scale-centre 1, w = kappa*dt/h^2
                           wave, velocity model     u' = 2u + v*L(u) - u_old   --scale --scale-centre 2 --time-order 2, w = v^2*dt^2/h^2
                           Jacobi, variable diagonal u' = A(u)/d + f/d          --scale --source, S the off-diagonal average, w = 1/diag, src = f/diag
+--varcoef               One coefficient array per tap: a launch takes one more array coef of the grid's dtype and shape (T, L, M, N) -- (T, M, N)
+                        in 2D --, T the taps of the one-step stencil in gold order (the kernel info lists them: "coef_taps"), and computes
+                        at every interior point p  v = a_0[p] * in[p + d_0];  v = fma(a_t[p], in[p + d_t], v), t = 1 .. T-1  -- the
+                        unchanged FMA chain, the array value in the constant's place -- in front of the other options' operations.  The
+                        .stc constants define the shape and the tap order only.  Each of the T grids is read in its interior only, each
+                        value reaching only its own cell and tap; coef is never written and must not overlap out.  With a_t = the
+                        constant as it is written everywhere, the stored bits are those of the same command without the option.  The
+                        kernel is dr_<name>(in, out, [src,] [res,] [fix,] [w,] coef) and the plugin exports drs_plugin_launch_ops /
+                        drs_plugin_launch_gold_ops with one more pointer.  Needs --step 1; not with --temporal, --gpus N > 1,
+                        --pair-launch 1, --coef or --pack 1.  Without a geometry option the tuner's row is stepped down
+                        until the T coefficient values per point fit the register file (rows per lane, then points per row, then --by).
+                          heterogeneous diffusion  u' = u + dt*div(k grad u)   a_t = dt*k(face t)/h^2, a_centre = 1 - their sum
+                          anisotropic operator     u' = sum a_t(p) u(p + d_t)  a_t from the local tensor (rotated, stretched)
+                          Jacobi, stencil-form A   u' = (f - R u)/diag         --varcoef --source, a_t = -A_t/diag, a_centre = 0, src = f/diag
 --xrim <lds|dpp>        x halo inside a wavefront by DPP wave shifts (default) or through LDS.
 --schedule <scatter|reuse|window>  How reuse along the streamed dimension is split between source planes kept on chip and
                         partial sums carried in VGPRs (results never depend on it):
@@ -282,6 +296,7 @@ struct Opt {
 inline bool put_coef(GenOptions &o, const std::string &v) {
     const int c = v == "lit" ? 0 : v == "sgpr" ? 1 : v == "vgpr" ? 2 : -1;
     if (c >= 0) o.coef_sgpr = c;
+    o.coef_set = true;
     return c >= 0;
 }
 inline bool put_temporal(GenOptions &o, const std::string &v) {
@@ -317,6 +332,7 @@ inline constexpr Opt kOptions[] = {
     {"--time-order", &GenOptions::time_order, NAMES}, {"--source", &GenOptions::source, NAMES},
     {"--residual", &GenOptions::residual, "max", NAMES, &GenOptions::residual_set}, {"--dirichlet", &GenOptions::dirichlet, NAMES},
     {"--scale", &GenOptions::scale, NAMES}, {"--scale-centre", put_scale_centre, NAMES},
+    {"--varcoef", &GenOptions::varcoef, NAMES},
     {"--gpus", &GenOptions::gpus, NAMES | LOCAL}, {"--pair-launch", &GenOptions::pair_launch, NAMES}, {"--temporal", put_temporal, NAMES},
     {"--out-skew", &GenOptions::out_skew, NAMES}, {"--tuned-defaults", &GenOptions::tuned_defaults, NAMES},
     {"--schedule", &GenOptions::schedule, "scatter reuse window", 0, &GenOptions::schedule_set},
@@ -384,6 +400,7 @@ inline bool scan_options(const std::vector<std::string> &args, GenResult &res, s
         if (a == "--time-order" && o.time_order == 1) continue;       // likewise
         if (a == "--dirichlet") continue;                             // echoed once, behind every other option (below)
         if (a == "--scale" || a == "--scale-centre") continue;        // likewise, behind --dirichlet
+        if (a == "--varcoef") continue;                               // likewise, behind every other option
         echo(a, !(r->attr & LOCAL));
         if (!flag) echo(v, !(r->attr & LOCAL));
     }
@@ -405,6 +422,7 @@ inline bool scan_options(const std::vector<std::string> &args, GenResult &res, s
         words.push_back({"--scale-centre", true, false});
         words.push_back({coef_text(o.scale_centre), true, false});
     }
+    if (o.varcoef) words.push_back({"--varcoef", true, false});
     for (auto &e : words) { banner += (banner.empty() ? "" : " ") + e.w; if (e.slab) o.slab_args.push_back(e.w); }
     return true;
 }
@@ -416,6 +434,8 @@ inline GenResult generate(const std::vector<std::string> &args /* argv[1..] */) 
     std::string banner;
     if (!scan_options(args, res, banner)) return res;
     GenOptions &o = res.opt;
+    const bool bare = !o.tuning_given && !o.ref_defaults;      // no geometry / emission option on the command line (the --varcoef fit rule below)
+    std::vector<std::string> full_args = args;                 // the command as it is planned: with the tuner's row, if one is found
 
     const std::string &stcfile = args.back();
     Stencil &st = res.st;
@@ -434,6 +454,7 @@ inline GenResult generate(const std::vector<std::string> &args /* argv[1..] */) 
             again.insert(again.end(), {"--tuned-defaults", "0", stcfile});
             res.tuned_from = t->options;
             if (!scan_options(again, res, banner)) return res;
+            full_args = again;
         }
     }
     st.fuse(o.step);
@@ -445,13 +466,67 @@ inline GenResult generate(const std::vector<std::string> &args /* argv[1..] */) 
     // faster AND is what makes the kernel fit at all: fused 3D stencils beyond 25 taps (--step 3: 256 VGPRs + scratch in the taps order,
     // 98-114 in the rows order; 1880-2080 against 430 GStencil/s at 1024^3) and one-shot 2D tiles of more than 9 taps (2d25pt_box: +6 %,
     // profiles/r03_exp_r3d.log).  Everything else keeps round 2's emission, which measured faster there (the memory-bound step-2 headline).
-    if (!o.order_set && !o.ref_defaults && !o.temporal && o.schedule == "scatter" && o.stage == "reg" && std::max(o.bmy, o.cmy) == std::max(o.bmy, 1) &&
-        !(o.cmx > 1 && o.cmx >= o.bmx) &&
-        ((st.ndim == 3 && st.pts.size() > 25) || (st.ndim == 2 && !o.streaming && st.pts.size() > 9))) {
-        o.order = "rows";
-        if (o.pack < 0) o.pack = 0;       // packed pairs buy nothing with four waves per SIMD
-    }
+    // (applied after EVERY scan of the options -- the fit rule below scans again --, so that a command and the command its banner spells
+    // out take the same defaults)
+    auto emission_defaults = [&]() {
+        if (!o.order_set && !o.ref_defaults && !o.temporal && o.schedule == "scatter" && o.stage == "reg" && std::max(o.bmy, o.cmy) == std::max(o.bmy, 1) &&
+            !(o.cmx > 1 && o.cmx >= o.bmx) &&
+            ((st.ndim == 3 && st.pts.size() > 25) || (st.ndim == 2 && !o.streaming && st.pts.size() > 9))) {
+            o.order = "rows";
+            if (o.pack < 0) o.pack = 0;       // packed pairs buy nothing with four waves per SIMD
+        }
+        if (o.varcoef && o.pack < 0) o.pack = 0;       // a packed pair takes ONE constant for both halves: unpacked is the default under --varcoef
+    };
+    emission_defaults();
     res.plan = make_plan(st, o, kernel_base_name(stcfile));
+    // ---- the --varcoef fit rule.  T coefficient values per point stand in registers from their loads (in front of the plane's barrier) to
+    // their FMAs: T * points-per-lane words (twice that in fp64) on top of the sweep's state.  A geometry the tuner chose for two arrays does
+    // not hold them (C4: 139 VGPRs + 7 x 16), and the runtime refuses kernels that spill.  So where the command names no geometry, the
+    // generator steps the planned geometry down, deterministically, until Schedule::reg_demand() plus 32 registers of addressing fits what a
+    // lane can have at the workgroup's size (at most 256: no AGPR spilling): rows per lane halved down to 1, then points per row down to
+    // one vector, then --by.  Each step plans the same command with the whole geometry spelled out ONCE behind the command's own words, so
+    // banner, info and cache key are those of the explicit command line, and the banner's command emits this source again.  The margin of
+    // 32 is not fitted to the compiler's reports.  A geometry given explicitly is taken as given
+    std::string stepped_from, stepped_to;
+    if (bare && o.varcoef && res.plan.error.empty()) {
+        auto geometry = [](const KernelPlan &p) {
+            std::vector<std::string> w = {"--bx", std::to_string(p.BX), "--by", std::to_string(p.BY), p.cyclic_x ? "--cyclic-merge-x" : "--block-merge-x", std::to_string(p.VX)};
+            if (p.has_y) { w.push_back(p.cyclic_y ? "--cyclic-merge-y" : "--block-merge-y"); w.push_back(std::to_string(p.RY)); }
+            if (p.has_s) { w.push_back("--sn"); w.push_back(std::to_string(p.SN)); }
+            return w;
+        };
+        auto budget = [](const KernelPlan &p) { const int per_simd = ceil_div(ceil_div(p.NT + 64 * p.ws, 64), 4); return std::min(256, 512 / std::max(1, per_simd) / 8 * 8); };
+        const std::vector<std::string> base_args = full_args;            // the command as planned first: every step starts from it
+        const bool add_prefetch = res.plan.prefetch && !o.prefetch;      // the planner's default had it: the spelled-out geometry skips that default
+        for (int round = 0; round < 16; round++) {
+            KernelPlan &p = res.plan;
+            const int demand = Schedule(p, o).reg_demand() + 32;
+            if (demand <= budget(p)) break;
+            KernelPlan q = p;      // the next smaller geometry
+            if (p.RY > 1) q.RY = p.RY / 2;
+            else if (p.VX > (p.fp32 ? 4 : 2) && p.VX % 2 == 0) q.VX = p.VX / 2;
+            else if (p.BY > 1) q.BY = p.BY / 2;
+            else break;
+            if (stepped_from.empty()) stepped_from = joined(geometry(p)) + " (" + std::to_string(demand) + " registers per lane of " + std::to_string(budget(p)) + ")";
+            // (the command itself names no geometry: such words in it are the tuner's row's, and give way to the geometry spelled out here)
+            std::vector<std::string> again;
+            for (size_t i = 0; i + 1 < base_args.size(); i++) {
+                static const char *const geo[] = {"--bx", "--by", "--sn", "--block-merge-x", "--cyclic-merge-x", "--block-merge-y", "--cyclic-merge-y"};
+                if (std::find_if(std::begin(geo), std::end(geo), [&](const char *g) { return base_args[i] == g; }) != std::end(geo)) { i++; continue; }
+                again.push_back(base_args[i]);
+            }
+            for (auto &w : geometry(q)) again.push_back(w);
+            if (add_prefetch) again.push_back("--prefetch");
+            if (std::find(again.begin(), again.end(), "--tuned-defaults") == again.end()) again.insert(again.end(), {"--tuned-defaults", "0"});
+            again.push_back(stcfile);
+            full_args = again;
+            if (!scan_options(again, res, banner)) return res;
+            emission_defaults();
+            res.plan = make_plan(st, o, kernel_base_name(stcfile));
+            if (!res.plan.error.empty()) break;
+            stepped_to = joined(geometry(res.plan));
+        }
+    }
     if (!res.plan.error.empty()) { res.messages += "Invalid configuration!\n"; res.exit_code = 255; res.error = res.plan.error; return res; }
     if (!res.plan.note.empty()) res.messages += "drstencil: note: " + res.plan.note + "\n";
     if (o.gpus < 1 || o.gpus > 64) { res.messages += "Illegal input.\n"; res.exit_code = 255; return res; }
@@ -493,6 +568,13 @@ inline GenResult generate(const std::vector<std::string> &args /* argv[1..] */) 
         res.messages += "Invalid configuration!\n"; res.exit_code = 255;
         res.error = o.gpus > 1 ? "--dirichlet cannot be combined with --gpus N > 1 (the slab runtime passes no view of an array of held cells)"
                                : "--dirichlet cannot be combined with --pair-launch 1 (the pair kernel serves the slab runtime, which has no held cells)";
+        return res;
+    }
+    if (res.plan.varcoef && (o.gpus > 1 || o.pair_launch)) {
+        // the slab views are windows of two arrays; views of the coefficient grids are no part of the slab runtime, and the pair kernel serves it
+        res.messages += "Invalid configuration!\n"; res.exit_code = 255;
+        res.error = o.gpus > 1 ? "--varcoef cannot be combined with --gpus N > 1 (the slab runtime passes no views of the coefficient grids)"
+                               : "--varcoef cannot be combined with --pair-launch 1 (the pair kernel serves the slab runtime, which has no coefficient arrays)";
         return res;
     }
     if (res.plan.scale && (o.gpus > 1 || o.pair_launch)) {
@@ -549,6 +631,12 @@ inline GenResult generate(const std::vector<std::string> &args /* argv[1..] */) 
     if (res.plan.scale)
         res.notes += std::string("drstencil: note: per-cell factor: a launch takes one more array w and computes ") +
                      (res.plan.centre_term() ? "(" + res.plan.scale_centre + ") * in + w * S(in)" : std::string("w * S(in)")) + " on the interior, in front of the other options' operations (w is read only, in its interior)\n";
+    if (res.plan.varcoef)
+        res.notes += "drstencil: note: per-tap coefficients: a launch takes one more array coef of " + std::to_string(res.plan.taps.size()) +
+                     " grids, tap t's in grid t (gold order, \"coef_taps\" in the kernel info), and computes sum_t coef[t][p] * in[p + d_t] as the FMA chain; the .stc constants are not used (coef is read only, in its interior)\n";
+    if (!stepped_to.empty())
+        res.notes += "drstencil: note: --varcoef: no geometry option given and " + stepped_from + " does not hold the " + std::to_string(res.plan.taps.size()) +
+                     " coefficient values per point; stepped down to " + stepped_to + "\n";
     if (!res.tuned_from.empty())
         res.notes += "drstencil: note: no geometry option given: the tuner's configuration for this stencil, step, dtype and grid size is used (" +
                      res.tuned_from + "); --tuned-defaults 0 keeps the generic defaults\n";

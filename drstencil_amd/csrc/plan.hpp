@@ -200,6 +200,11 @@ struct GenOptions {
     double scale_centre = 0.0;   // --scale-centre c (needs --scale): v = C * in[p] + w[p] * S(in)[p], a rounded product and a rounded sum, C being c as
                                  // the emitted source writes coefficients (coef_text).  0: no centre term, the centre values are not loaded for it
     bool scale_centre_set = false;
+    bool varcoef = false;        // --varcoef: a launch takes one more read-only array coef of shape (T, grid), T the taps of the one-step stencil in gold
+                                 // order, and computes v = sum_t coef[t][p] * in[p + d_t] as the same FMA chain, the array value in the constant's
+                                 // place.  The .stc constants define the shape and the tap order only.  T more memory streams of the sweep, each
+                                 // read once.  It names the problem, not a tuning choice
+    bool coef_set = false;       // --coef given (--varcoef refuses it)
 };
 
 // ---- boundary modes per axis (0 z, 1 y, 2 x; z counts as fixed in 2D)
@@ -278,6 +283,7 @@ struct KernelPlan {
     std::string scale_centre;    // --scale-centre c != 0: the coefficient's text (coef_text), v = C * in + w * S(in); empty: no centre term
     bool centre_term() const { return !scale_centre.empty(); }
     bool centre_live() const { return residual || centre_term(); }      // the input's centre values are a stream of the sweep (one family of sets, whoever needs them)
+    bool varcoef = false;        // --varcoef: tap t's coefficient is coef[t][p], read at the cell that takes the sum (taps in gold order; the interior of each of the T grids is read, each value reaching only its own cell and tap)
     std::string error;       // non-empty: invalid configuration
     std::string note;        // non-empty: something the user asked for was not done (printed by the generator, kept in the banner)
 };

@@ -308,6 +308,13 @@ inline KernelPlan make_plan(const Stencil &st, const GenOptions &o_in, const std
     if (p.scale && o_in.step > 1) { p.error = "--scale needs --step 1 (a fused S^n scaled once is not n scaled steps)"; return p; }
     if (p.scale && o_in.temporal) { p.error = "--scale cannot be combined with --temporal (on-chip stages fuse time steps; every scaled step multiplies by the factor)"; return p; }
     if (p.scale && coef_rounded(o.scale_centre) != 0.0) p.scale_centre = coef_text(o.scale_centre);
+    // --varcoef: the coefficients are taken at the cell that takes the sum; a fused S^n has no such cell for its inner steps
+    p.varcoef = o.varcoef;
+    if (p.varcoef && o_in.step > 1) { p.error = "--varcoef needs --step 1 (a fused S^n with coefficients taken at one cell is not n variable-coefficient steps)"; return p; }
+    if (p.varcoef && o_in.temporal) { p.error = "--varcoef cannot be combined with --temporal (on-chip stages fuse time steps; every step takes its coefficients at its own cells)"; return p; }
+    if (p.varcoef && o.coef_set) { p.error = "--varcoef cannot be combined with --coef (the coefficients are array values: there are no kernel constants to place)"; return p; }
+    if (p.varcoef && o.pack > 0) { p.error = "--varcoef cannot be combined with --pack 1 (packed pairs take one constant for both halves; --pack 0 is the default with --varcoef)"; return p; }
+    if (p.varcoef && o.debug_skip) { p.error = "--varcoef is not available with --debug-skip"; return p; }
     if (p.residual && o_in.temporal) { p.error = "--residual cannot be combined with --temporal (on-chip stages keep the intermediate steps on the chip: the sweep that stores never holds the input's centre values)"; return p; }
 
     if (o.loader_waves > 0 && o.stage != "dma") { p.error = "--loader-waves goes with --stage dma"; return p; }

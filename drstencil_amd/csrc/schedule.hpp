@@ -78,7 +78,14 @@ struct Schedule {
     // 32-bit registers of the per-lane state the kernel names: partial sums, register windows (own points + rims) and the
     // prefetch sets.  The tuner's FilterParams compares it with the register file a lane can have at the workgroup's size
     // (drstencil_amd/tuner/tuning.py: fitted against the compiler's resource reports, profiles/r02_reg_model.md).
-    int reg_demand() const { return reg_demand_sweep() + (p.fp32 ? 1 : 2) * (extra_streams() * old_sets() * p.RY * p.VX + residual_words()); }
+    int reg_demand() const { return reg_demand_sweep() + (p.fp32 ? 1 : 2) * (extra_streams() * old_sets() * p.RY * p.VX + residual_words() + coef_words()); }
+    // ---- --varcoef: tap t's coefficient at every cell the lane stores is one more stream of that kind per tap, from grid t of coef
+    // (kv<t>_0_<r>_<q>), under the store's guards -- but with a plane lead of its own and at distance 0: in iteration u the arriving source
+    // plane adds its taps of streamed offset ds to output plane k + u + (zh - ds), so tap t's values are loaded zh - t.ds planes ahead of the
+    // plane pout points at, in front of the iteration's barrier, and meet their FMAs behind it.  One set: T * RY * VX elements live across
+    // the barrier (they do not join extra_streams(): the other streams keep their distance and their sets).  The prologue iterations load
+    // theirs the same way, from the block's first planes.
+    int coef_words() const { return p.varcoef ? (int)p.taps.size() * p.RY * p.VX : 0; }
     // ---- --time-order 2: the old output, the sweep's third memory stream -----------------------------------------------------------
     // out = S(in) - out_old.  The old vector of every (r, q) the lane stores is loaded into named registers ov<set>_<r>_<q>, under the
     // store's own guards, old_dist() planes AHEAD of the iteration that completes and stores that plane: with --prefetch at the prefetch

@@ -188,6 +188,7 @@ drs_slab *drs_slab_open(int argc, const char *const *argv, int alone_argc, const
     GenResult r = generate(to_args(argc, argv));
     if (!r.emitted) return fail(r.messages + (r.error.empty() ? "" : ("drstencil: " + r.error)));
     if (r.plan.source) return fail("drs_slab_open: --source is not supported by the slab runtime (it passes no view of a source array)");
+    if (r.plan.varcoef) return fail("drs_slab_open: --varcoef is not supported by the slab runtime (it passes no views of the coefficient grids)");
     if (r.plan.scale) return fail("drs_slab_open: --scale is not supported by the slab runtime (it passes no view of an array of factors)");
     if (r.plan.dirichlet) return fail("drs_slab_open: --dirichlet is not supported by the slab runtime (it passes no view of an array of held cells)");
     if (r.plan.residual) return fail("drs_slab_open: --residual is not supported by the slab runtime (it passes no residual array and reduces nothing over the ranks)");

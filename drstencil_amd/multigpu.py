@@ -89,6 +89,12 @@ def refuse_scale(opts, who):
         raise ValueError("%s: --scale is not supported by the slab decomposition (it passes no view of an array of per-cell factors); run it on one GPU" % who)
 
 
+def refuse_varcoef(opts, who):
+    """--varcoef has no slab form: the slab classes pass views of two arrays, none of the coefficient grids."""
+    if "--varcoef" in list(opts or ()):
+        raise ValueError("%s: --varcoef is not supported by the slab decomposition (it passes no views of the coefficient grids); run it on one GPU" % who)
+
+
 def slab_bounds(L, world, rank):
     """Planes [z0, z1) owned by `rank` (balanced split of the outermost dim)."""
     return (rank * L) // world, ((rank + 1) * L) // world
@@ -336,11 +342,13 @@ class HipSweep:
         refuse_source(opts, "HipSweep")
         refuse_dirichlet(opts, "HipSweep")
         refuse_scale(opts, "HipSweep")
+        refuse_varcoef(opts, "HipSweep")
         refuse_residual(opts, "HipSweep")
         refuse_second_order(alone_opts, "HipSweep")
         refuse_source(alone_opts, "HipSweep")
         refuse_dirichlet(alone_opts, "HipSweep")
         refuse_scale(alone_opts, "HipSweep")
+        refuse_varcoef(alone_opts, "HipSweep")
         refuse_residual(alone_opts, "HipSweep")
         self.base_stc, self.opts, self.cache_dir = base_stc, list(opts), cache_dir
         self.alone_opts = list(alone_opts) if alone_opts else None
@@ -459,6 +467,7 @@ class SlabRun:
         refuse_source(getattr(sweep, "opts", None), "SlabRun")
         refuse_dirichlet(getattr(sweep, "opts", None), "SlabRun")
         refuse_scale(getattr(sweep, "opts", None), "SlabRun")
+        refuse_varcoef(getattr(sweep, "opts", None), "SlabRun")
         refuse_residual(getattr(sweep, "opts", None), "SlabRun")
         self.torch, self.dist = torch, dist
         dims = tuple(dims)
@@ -654,11 +663,13 @@ class NativeSlabRun:
         refuse_source(opts, "NativeSlabRun")
         refuse_dirichlet(opts, "NativeSlabRun")
         refuse_scale(opts, "NativeSlabRun")
+        refuse_varcoef(opts, "NativeSlabRun")
         refuse_residual(opts, "NativeSlabRun")
         refuse_second_order(alone_opts, "NativeSlabRun")
         refuse_source(alone_opts, "NativeSlabRun")
         refuse_dirichlet(alone_opts, "NativeSlabRun")
         refuse_scale(alone_opts, "NativeSlabRun")
+        refuse_varcoef(alone_opts, "NativeSlabRun")
         refuse_residual(alone_opts, "NativeSlabRun")
         self.torch, self.dist = torch, dist
         dims = tuple(dims)

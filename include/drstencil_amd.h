@@ -72,6 +72,7 @@ int drs_kernel_unload(drs_kernel *k);
  *   "source": 1                    only for kernels generated with --source (see drs_kernel_launch_src).
  *   "dirichlet": 1                 only for kernels generated with --dirichlet (see drs_kernel_launch_fix).
  *   "scale": 1, "scale_centre": C  only for kernels generated with --scale (see drs_kernel_launch_ops): C is 0 without a centre term.
+ *   "varcoef": 1, "coef_taps": [[k,j,i],...]   only for kernels generated with --varcoef (see drs_kernel_launch_ops): tap t of coef, gold order.
  *   "residual": "max", "residual_elems": N   only for kernels generated with --residual max (see drs_kernel_launch_res): N = 1 + "grid". */
 const char *drs_kernel_info(const drs_kernel *k);
 const char *drs_kernel_path(const drs_kernel *k);   /* the loaded shared object */
@@ -216,6 +217,7 @@ int drs_kernel_solve_fix(drs_kernel *k, void *d_a, void *d_b, const void *d_src,
  *   res    --residual max   drs_kernel_residual_elems(k) elements, written whole by every launch
  *   fix    --dirichlet      read only, the grid's shape and dtype
  *   scale  --scale          read only, the grid's shape and dtype
+ *   coef   --varcoef        read only, T grids of the grid's shape and dtype, tap t's first (see below)
  * -2 (the "wrong kind" code of every family): size is not sizeof(drs_operands), a pointer the kernel needs is NULL, or a pointer the kernel
  * does not take is non-NULL.  The gold kernel computes no residual: the gold forms leave res alone, and accept one only on a --residual
  * max kernel.  -1 is a HIP error, -3 as drs_kernel_run.
@@ -228,8 +230,22 @@ int drs_kernel_solve_fix(drs_kernel *k, void *d_a, void *d_b, const void *d_src,
  * term the stored bits are those of the same command without the option.
  * Such a plugin exports drs_plugin_launch_ops / drs_plugin_launch_gold_ops INSTEAD of every other launch entry point: every entry point
  * above (the plain, _src, _res and _fix families and drs_kernel_solve) returns -2 on it; it runs through the five below only.
- * --step n > 1, --temporal, --gpus N > 1, --pair-launch 1 and the drs_slab_* runtime refuse --scale. */
-typedef struct { size_t size; const void *src; void *res; const void *fix; const void *scale; } drs_operands;
+ * --step n > 1, --temporal, --gpus N > 1, --pair-launch 1 and the drs_slab_* runtime refuse --scale.
+ * --varcoef: a kernel generated with --varcoef is dr_<name>(in, out[, src][, res][, fix][, w], coef).  coef has the grid's dtype and shape
+ * (T, L, M, N) -- (T, M, N) in 2D --, T = "taps"; grid t starts at element t * L * M * N (64-bit offsets) and holds the coefficient of tap t
+ * of the gold sum, the taps being listed by "coef_taps" / drs_kernel_coef_taps.  At every interior point p
+ *   v = a_0[p] * in[p + d_0];  v = fma(a_t[p], in[p + d_t], v), t = 1 .. T-1
+ * -- the unchanged chain with the array value in the constant's place; the .stc constants give the shape and the order only -- and then
+ * the operations above in their order.  Only the INTERIOR of each grid is read, each value reaching only its own cell and its own tap;
+ * coef is never written, must not overlap d_out and follows the alignment rule of the other arrays.  With a_t = the constant as it is
+ * written, everywhere, the stored bits are those of the same command without the option.  Such a kernel runs through the five entry
+ * points below only: every suffixed family and the plain entry points return -2 on it.  --step n > 1, --temporal, --gpus N > 1,
+ * --pair-launch 1, --coef, --pack 1 and the drs_slab_* runtime refuse --varcoef.
+ * The block grew by its trailing field `coef` with --varcoef, and size is still checked strictly: a caller compiled against the older,
+ * shorter block gets -2 from every _ops entry point -- never a read past its block -- and has to be recompiled. */
+typedef struct { size_t size; const void *src; void *res; const void *fix; const void *scale; const void *coef; } drs_operands;
+/* "[[k,j,i],...]": the taps of a --varcoef kernel in the order of coef's grids (k = 0 in 2D); NULL for any other kernel.  Owned by k. */
+const char *drs_kernel_coef_taps(const drs_kernel *k);
 /* one launch (in -> out), asynchronous on `stream` */
 int drs_kernel_launch_ops(drs_kernel *k, const void *d_in, void *d_out, const drs_operands *ops, void *stream);
 /* gold_<name> with the same operands */

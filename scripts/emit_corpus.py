@@ -284,8 +284,41 @@ def scale_lists():
     return [(None, l) for l in lists] + [(None, j) for j in scale_cases.all_build_args()]       # what build() emits for the scale tests
 
 
+def varcoef_lists():
+    """--varcoef.  Behind everything else, so that the lists in front keep their numbers: against a build without the option `diff -r`
+    shows these files (and --help) and nothing else."""
+    import varcoef_cases
+    vc3 = ["--3d", "--dtype", "fp32", "--varcoef", "--check"]
+    cfg = os.path.join(ROOT, "benchmarks", "configs")
+    lists = [
+        # the emitted main() with the coefficient grids, every issue point of the coefficient loads, a sum that starts late, five leads,
+        # the reuse and window schedules, all streams at once
+        vc3 + [stc("t3_wave")], vc3 + ["--store-mask", "buffer", stc("t3_wave")], vc3 + ["--prefetch", "--prefetch-depth", "2", stc("t3_wave")],
+        vc3 + ["--stage", "dma", stc("t3_wave")], vc3 + ["--order", "rows", "--defer-stores", "1", "--prefetch", stc("t3_wave")],
+        vc3 + ["--by", "4", "--block-merge-y", "2", stc("t3_ahead")], vc3 + ["--by", "8", "--block-merge-y", "1", stc("shape_11_3d_o2")],
+        vc3 + ["--dist", "1", stc("t3_wave")], vc3 + ["--schedule", "window", stc("t3_wave")],
+        vc3 + ["--source", "--time-order", "2", "--residual", "max", "--dirichlet", "--scale", "--scale-centre", "0.3", "--prefetch", stc("t3_wave")],
+        ["--dtype", "fp64", "--varcoef", "--check", stc("lap2")], ["--dtype", "fp32", "--varcoef", "--streaming", "--boundary", "reflect", stc("t2_ahead")],
+        ["--dtype", "fp64", "--varcoef", "--streaming", "--stage", "dma", stc("t2_box25")],
+        # the option has one place in the banner; the bare benchmark commands (the fit rule)
+        ["--varcoef", "--3d", "--varcoef", "--dtype", "fp32", stc("t3_wave")],
+        ["--dtype", "fp32", "--varcoef", os.path.join(cfg, "c1_2d5pt_star_4096.stc")], ["--dtype", "fp32", "--varcoef", os.path.join(cfg, "c2_2d5pt_star_8192.stc")],
+        ["--3d", "--dtype", "fp32", "--varcoef", os.path.join(cfg, "c3_3d7pt_star_512.stc")], ["--3d", "--dtype", "fp32", "--varcoef", os.path.join(cfg, "c4_3d7pt_star_1024.stc")],
+        ["--dtype", "fp64", "--varcoef", os.path.join(cfg, "c5_2d25pt_box_16384.stc")],
+        # rejected before the emitter is asked
+        ["--3d", "--varcoef", "--step", "2", stc("t3_star")], ["--3d", "--varcoef", "--temporal", "force", stc("t3_star")], ["--3d", "--varcoef", "--gpus", "2", stc("t3_star")],
+        ["--3d", "--varcoef", "--pair-launch", "1", stc("t3_star")], ["--3d", "--dtype", "fp32", "--varcoef", "--coef", "sgpr", stc("t3_star")],
+        ["--3d", "--dtype", "fp32", "--varcoef", "--order", "rows", "--pack", "1", stc("t3_star")],
+    ]
+    for b in ("d3", "d3f64", "rows", "tile", "cross", "stream", "odd"):
+        opts, name = BASES[b]
+        if "--pack" not in opts:
+            lists.append(list(opts) + ["--varcoef", stc(name)])
+    return [(None, l) for l in lists] + [(None, j) for j in varcoef_cases.all_build_args()]       # what build() emits for the varcoef tests
+
+
 def corpus():
-    return build_lists() + space_sample() + host_lists() + knob_lists() + boundary_lists() + source_lists() + residual_lists() + dirichlet_lists() + scale_lists()
+    return build_lists() + space_sample() + host_lists() + knob_lists() + boundary_lists() + source_lists() + residual_lists() + dirichlet_lists() + scale_lists() + varcoef_lists()
 
 
 def coverage(lists):
