@@ -244,54 +244,28 @@ class Kernel:
         self.resources = json.loads(lib().drs_kernel_resources(self.h).decode() or "{}")   # registers / scratch / LDS per the compiler
         self.args = list(args)
 
-    def _src(self, d_src, who):
-        """The source array of a call, checked against the kernel: a --source kernel needs one, a plain kernel takes none."""
-        if self.source and not d_src:
-            raise ValueError("%s(): the kernel was generated with --source and needs d_src, the source array" % who)
-        if not self.source and d_src is not None:
-            raise ValueError("%s(): d_src given, but the kernel was generated without --source" % who)
-        return d_src
+    # the arrays a launch takes beside in and out, in the order of drs_operands: (keyword d_<name>, the Kernel property that says whether the
+    # kernel takes it, the option that makes it, what it is)
+    _OPERANDS = (("src", "source", "--source", "the source array"),
+                 ("res", "residual_elems", "--residual", "an array of residual_elems elements"),
+                 ("fix", "dirichlet", "--dirichlet", "the array of held cells"),
+                 ("scale", "scale", "--scale", "the array of per-cell factors"),
+                 ("coef", "varcoef", "--varcoef", "the array of per-tap coefficients, shape (%d,) + grid"))
 
-    def _res(self, d_res, who):
-        """The residual array of a call, checked against the kernel: a --residual kernel needs one, any other kernel takes none."""
-        if self.residual_elems and not d_res:
-            raise ValueError("%s(): the kernel was generated with --residual and needs d_res, an array of residual_elems elements" % who)
-        if not self.residual_elems and d_res is not None:
-            raise ValueError("%s(): d_res given, but the kernel was generated without --residual" % who)
-        return d_res
+    def _operand(self, row, d, who):
+        """One array of a call, checked against the kernel: a kernel generated with the array's option needs it, any other kernel takes none."""
+        name, taken, option, what = row
+        if getattr(self, taken) and not d:
+            raise ValueError("%s(): the kernel was generated with %s and needs d_%s, %s" % (who, option, name, what % len(self.coef_taps) if name == "coef" else what))
+        if not getattr(self, taken) and d is not None:
+            raise ValueError("%s(): d_%s given, but the kernel was generated without %s" % (who, name, option))
+        return d
 
-    def _fix(self, d_fix, who):
-        """The array of held cells of a call, checked against the kernel: a --dirichlet kernel needs one, any other kernel takes none."""
-        if self.dirichlet and not d_fix:
-            raise ValueError("%s(): the kernel was generated with --dirichlet and needs d_fix, the array of held cells" % who)
-        if not self.dirichlet and d_fix is not None:
-            raise ValueError("%s(): d_fix given, but the kernel was generated without --dirichlet" % who)
-        return d_fix
-
-    def _scale(self, d_scale, who):
-        """The array of per-cell factors of a call, checked against the kernel: a --scale kernel needs one, any other kernel takes none."""
-        if self.scale and not d_scale:
-            raise ValueError("%s(): the kernel was generated with --scale and needs d_scale, the array of per-cell factors" % who)
-        if not self.scale and d_scale is not None:
-            raise ValueError("%s(): d_scale given, but the kernel was generated without --scale" % who)
-        return d_scale
-
-    def _coef(self, d_coef, who):
-        """The coefficient grids of a call, checked against the kernel: a --varcoef kernel needs them, any other kernel takes none."""
-        if self.varcoef and not d_coef:
-            raise ValueError("%s(): the kernel was generated with --varcoef and needs d_coef, the array of per-tap coefficients, shape (%d,) + grid" % (who, len(self.coef_taps)))
-        if not self.varcoef and d_coef is not None:
-            raise ValueError("%s(): d_coef given, but the kernel was generated without --varcoef" % who)
-        return d_coef
-
-    def _ops(self, who, d_src, d_res, d_fix, d_scale, gold=False, d_coef=None):
-        """The operand block (drs_operands) of a call, every array checked against the kernel (the gold kernel computes no residual)."""
-        return ctypes.byref(Operands(ctypes.sizeof(Operands), self._src(d_src, who), None if gold else self._res(d_res, who), self._fix(d_fix, who),
-                                     self._scale(d_scale, who), self._coef(d_coef, who)))
-
-    def _by_ops(self, d_scale, d_coef, who):
-        """True when the call goes through the operand-block entry points: --scale and --varcoef kernels run through them only."""
-        return bool(self._scale(d_scale, who)) | bool(self._coef(d_coef, who))
+    def _ops(self, who, d_src, d_res, d_fix, d_scale, d_coef, gold=False):
+        """The operand block (drs_operands) of a call, every array checked against the kernel (the gold kernel computes no residual: its block
+        holds none).  Every launch of every kind of kernel goes through the operand-block entry points (drs_kernel_*_ops)."""
+        arrays = (d_src, d_res, d_fix, d_scale, d_coef)
+        return ctypes.byref(Operands(ctypes.sizeof(Operands), *[None if gold and r[0] == "res" else self._operand(r, d, who) for r, d in zip(self._OPERANDS, arrays)]))
 
     @property
     def varcoef(self):
@@ -335,7 +309,7 @@ class Kernel:
 
     def residual(self, d_res):
         """d_res[0] of a --residual kernel as a Python float (the device is synchronised by the copy): the residual of the last launch."""
-        if not self._res(d_res, "residual"):
+        if not self._operand(self._OPERANDS[1], d_res, "residual"):
             raise ValueError("residual(): the kernel was generated without --residual")
         v = ctypes.c_double()
         if lib().drs_kernel_residual(self.h, d_res, ctypes.byref(v)) != 0:
@@ -343,17 +317,12 @@ class Kernel:
         return float(v.value)
 
     def solve(self, d_a, d_b, d_res, tol, max_launches, check_every=8, d_src=None, stream=0, d_fix=None, d_scale=None, d_coef=None):
-        """Run to tolerance (drs_kernel_solve): ping-pong pairs k(A,B); k(B,A), `check_every` pairs between two looks at the residual, until
+        """Run to tolerance (drs_kernel_solve_ops): ping-pong pairs k(A,B); k(B,A), `check_every` pairs between two looks at the residual, until
         it is <= tol.  (status, launches, residual): status 0 converged, 1 max_launches (rounded down to an even number) reached, -4 the
-        residual is NaN or inf (a diverged or overflowed run).  The answer is in A.  --dirichlet kernels: d_fix, the held cells (drs_kernel_solve_fix)."""
-        self._res(d_res, "solve")
+        residual is NaN or inf (a diverged or overflowed run).  The answer is in A."""
         n, r = ctypes.c_int(), ctypes.c_double()
-        if self._by_ops(d_scale, d_coef, "solve"):
-            rc = lib().drs_kernel_solve_ops(self.h, d_a, d_b, self._ops("solve", d_src, d_res, d_fix, d_scale, d_coef=d_coef), tol, max_launches, check_every, stream, ctypes.byref(n), ctypes.byref(r))
-        elif self._fix(d_fix, "solve"):
-            rc = lib().drs_kernel_solve_fix(self.h, d_a, d_b, self._src(d_src, "solve"), d_res, d_fix, tol, max_launches, check_every, stream, ctypes.byref(n), ctypes.byref(r))
-        else:
-            rc = lib().drs_kernel_solve(self.h, d_a, d_b, self._src(d_src, "solve"), d_res, tol, max_launches, check_every, stream, ctypes.byref(n), ctypes.byref(r))
+        rc = lib().drs_kernel_solve_ops(self.h, d_a, d_b, self._ops("solve", d_src, d_res, d_fix, d_scale, d_coef), tol, max_launches, check_every, stream,
+                                        ctypes.byref(n), ctypes.byref(r))
         if rc == -2:
             raise ValueError("solve(): the kernel was generated without --residual, or check_every < 1")
         if rc == -1:
@@ -361,18 +330,10 @@ class Kernel:
         return rc, n.value, r.value
 
     def launch(self, d_in, d_out, stream=0, d_src=None, d_res=None, d_fix=None, d_scale=None, d_coef=None):
-        if self._by_ops(d_scale, d_coef, "launch"):
-            rc = lib().drs_kernel_launch_ops(self.h, d_in, d_out, self._ops("launch", d_src, d_res, d_fix, d_scale, d_coef=d_coef), stream)
-        elif self._fix(d_fix, "launch"):
-            rc = lib().drs_kernel_launch_fix(self.h, d_in, d_out, self._src(d_src, "launch"), self._res(d_res, "launch"), d_fix, stream)
-        elif self._res(d_res, "launch"):
-            rc = lib().drs_kernel_launch_res(self.h, d_in, d_out, self._src(d_src, "launch"), d_res, stream)
-        elif self._src(d_src, "launch"):
-            rc = lib().drs_kernel_launch_src(self.h, d_in, d_out, d_src, stream)
-        else:
-            rc = lib().drs_kernel_launch(self.h, d_in, d_out, stream)
+        rc = lib().drs_kernel_launch_ops(self.h, d_in, d_out, self._ops("launch", d_src, d_res, d_fix, d_scale, d_coef), stream)
         if rc != 0:
             raise RuntimeError("HIP launch error %d" % rc)
+
 
     def launch_pair(self, d_in0, d_out0, d_in1, d_out1, stream=0):
         """One launch over two (in, out) pairs (kernels generated with --pair-launch 1)."""
@@ -424,14 +385,7 @@ class Kernel:
             raise RuntimeError("HIP launch error %d" % rc)
 
     def launch_gold(self, d_in, d_out, stream=0, d_src=None, d_fix=None, d_scale=None, d_coef=None):
-        if self._by_ops(d_scale, d_coef, "launch_gold"):
-            rc = lib().drs_kernel_launch_gold_ops(self.h, d_in, d_out, self._ops("launch_gold", d_src, None, d_fix, d_scale, gold=True, d_coef=d_coef), stream)
-        elif self._fix(d_fix, "launch_gold"):
-            rc = lib().drs_kernel_launch_gold_fix(self.h, d_in, d_out, self._src(d_src, "launch_gold"), d_fix, stream)
-        elif self._src(d_src, "launch_gold"):
-            rc = lib().drs_kernel_launch_gold_src(self.h, d_in, d_out, d_src, stream)
-        else:
-            rc = lib().drs_kernel_launch_gold(self.h, d_in, d_out, stream)
+        rc = lib().drs_kernel_launch_gold_ops(self.h, d_in, d_out, self._ops("launch_gold", d_src, None, d_fix, d_scale, d_coef, gold=True), stream)
         if rc != 0:
             raise RuntimeError("HIP launch error %d" % rc)
 
@@ -439,34 +393,15 @@ class Kernel:
         """The reference's ping-pong loop (codegen.hpp:581-584); result ends in A.  --source kernels: the same d_src in every launch.
         --residual kernels: d_res[0] then holds the last launch's residual (the gold kernel computes none: gold=True takes no d_res)."""
         it = self.info["iterations"] if iterations is None else iterations
-        self._fix(d_fix, "run")
-        if self._by_ops(d_scale, d_coef, "run"):
-            if gold and d_res is not None:
-                raise ValueError("run(): the gold kernel computes no residual")
-            n = lib().drs_kernel_run_ops(self.h, d_a, d_b, self._ops("run", d_src, d_res, d_fix, d_scale, gold=gold, d_coef=d_coef), it, 1 if gold else 0, stream)
-        elif gold and self.residual_elems:
-            # gold_<name> keeps its entry point: the loop is made of single launches
-            if d_res is not None:
-                raise ValueError("run(): the gold kernel computes no residual")
-            n = 0
-            for t in range(0, it, 2 * self.info["step"]):
-                self.launch_gold(d_a, d_b, stream, d_src, d_fix)
-                self.launch_gold(d_b, d_a, stream, d_src, d_fix)
-                n += 2
-            return n
-        elif d_fix:
-            n = lib().drs_kernel_run_fix(self.h, d_a, d_b, self._src(d_src, "run"), self._res(d_res, "run"), d_fix, it, 1 if gold else 0, stream)
-        elif self._res(d_res, "run"):
-            n = lib().drs_kernel_run_res(self.h, d_a, d_b, self._src(d_src, "run"), d_res, it, stream)
-        elif self._src(d_src, "run"):
-            n = lib().drs_kernel_run_src(self.h, d_a, d_b, d_src, it, 1 if gold else 0, stream)
-        else:
-            n = lib().drs_kernel_run(self.h, d_a, d_b, it, 1 if gold else 0, stream)
+        if gold and d_res is not None:
+            raise ValueError("run(): the gold kernel computes no residual")
+        n = lib().drs_kernel_run_ops(self.h, d_a, d_b, self._ops("run", d_src, d_res, d_fix, d_scale, d_coef, gold=gold), it, 1 if gold else 0, stream)
         if n == -3:
             raise ToleranceHorizonExceeded(self._horizon_message(it))
         if n < 0:
             raise RuntimeError("HIP error in drs_kernel_run")
         return n
+
 
     def check_slabs(self, nsl):
         """Where a checker should look: [(label, first slice)] of `nsl`-slice slabs of the outermost dimension -- the bottom of the grid, a slab
@@ -494,21 +429,13 @@ class Kernel:
         """Warm-up launches + timed loop bracketed by HIP events on `stream`: (launches, ms)."""
         it = self.info["iterations"] if iterations is None else iterations
         ms = ctypes.c_float()
-        if self._by_ops(d_scale, d_coef, "run_timed"):
-            n = lib().drs_kernel_run_timed_ops(self.h, d_a, d_b, self._ops("run_timed", d_src, d_res, d_fix, d_scale, d_coef=d_coef), it, warmup, stream, ctypes.byref(ms))
-        elif self._fix(d_fix, "run_timed"):
-            n = lib().drs_kernel_run_timed_fix(self.h, d_a, d_b, self._src(d_src, "run_timed"), self._res(d_res, "run_timed"), d_fix, it, warmup, stream, ctypes.byref(ms))
-        elif self._res(d_res, "run_timed"):
-            n = lib().drs_kernel_run_timed_res(self.h, d_a, d_b, self._src(d_src, "run_timed"), d_res, it, warmup, stream, ctypes.byref(ms))
-        elif self._src(d_src, "run_timed"):
-            n = lib().drs_kernel_run_timed_src(self.h, d_a, d_b, d_src, it, warmup, stream, ctypes.byref(ms))
-        else:
-            n = lib().drs_kernel_run_timed(self.h, d_a, d_b, it, warmup, stream, ctypes.byref(ms))
+        n = lib().drs_kernel_run_timed_ops(self.h, d_a, d_b, self._ops("run_timed", d_src, d_res, d_fix, d_scale, d_coef), it, warmup, stream, ctypes.byref(ms))
         if n == -3:
             raise ToleranceHorizonExceeded(self._horizon_message(it))
         if n < 0:
             raise RuntimeError("HIP error in drs_kernel_run_timed")
         return n, ms.value
+
 
     def _horizon_message(self, it):
         return ("%d iterations exceed the tolerance horizon (%d) of this reassociated (temporal) kernel: build the fused kernel, or pass "

@@ -31,29 +31,16 @@ static bool g_launched = false;   // a kernel has been launched through this lib
 
 struct drs_kernel {
     void *dl = nullptr;
-    int (*launch)(const void *, void *, hipStream_t) = nullptr;
-    int (*launch_gold)(const void *, void *, hipStream_t) = nullptr;
+    // which arrays a launch takes and through which two symbols (plan.hpp): the families of entry points below accept a kernel by it
+    LaunchAbi abi;
+    void *sweep = nullptr, *gold = nullptr;      // abi.sweep_symbol() / abi.gold_symbol() of the plugin; launch_one() knows their signatures
+    int (*launch)(const void *, void *, hipStream_t) = nullptr;      // `sweep` of a PLAIN kernel, typed: the slab runtime (slab.hpp) calls it directly
     int (*launch_pair)(const void *, void *, const void *, void *, hipStream_t) = nullptr;   // only with --pair-launch 1
-    // --source kernels take a third, read-only array: their plugins export these INSTEAD of launch / launch_gold
-    int (*launch_src)(const void *, void *, const void *, hipStream_t) = nullptr;
-    int (*launch_gold_src)(const void *, void *, const void *, hipStream_t) = nullptr;
-    // --residual kernels: ONE sweep entry point with every array in its signature (src null unless --source), INSTEAD of launch / launch_src
-    int (*launch_res)(const void *, void *, const void *, void *, hipStream_t) = nullptr;
-    // --dirichlet kernels: these two, with every array in their signatures (src / res null unless --source / --residual), INSTEAD of all the others
-    int (*launch_fix)(const void *, void *, const void *, void *, const void *, hipStream_t) = nullptr;
-    int (*launch_gold_fix)(const void *, void *, const void *, const void *, hipStream_t) = nullptr;
-    // --scale kernels: these two, with every array in their signatures (null where the option is off), INSTEAD of all the others
-    int (*launch_ops)(const void *, void *, const void *, void *, const void *, const void *, hipStream_t) = nullptr;
-    int (*launch_gold_ops)(const void *, void *, const void *, const void *, const void *, hipStream_t) = nullptr;
-    // --varcoef kernels: the same two names with ONE MORE pointer (coef, behind scale); which signature a plugin has is known from the plan
-    int (*launch_opsk)(const void *, void *, const void *, void *, const void *, const void *, const void *, hipStream_t) = nullptr;
-    int (*launch_gold_opsk)(const void *, void *, const void *, const void *, const void *, const void *, hipStream_t) = nullptr;
-    bool has_coef = false;
-    std::string coef_taps;       // "[[k,j,i],...]" of a --varcoef kernel, else empty
-    long residual_elems = 0;     // elements of d_res (1 + launched workgroups); 0: no --residual
-    bool has_source = false, has_fix = false, has_scale = false, fp32 = false;
     int (*wrap)(void *, hipStream_t) = nullptr;              // only with a non-fixed boundary (--boundary periodic / reflect, --boundary-x / -y / -z)
     const char *(*info)(void) = nullptr;
+    std::string coef_taps;       // "[[k,j,i],...]" of a --varcoef kernel, else empty
+    long residual_elems = 0;     // elements of d_res (1 + launched workgroups); 0: no --residual
+    bool fp32 = false;
     std::string path;
     std::string resources;   // JSON: register / scratch / LDS use of dr_<name> as reported by the compiler
     int step = 1;
@@ -354,23 +341,14 @@ drs_kernel *drs_kernel_build(int argc, const char *const *argv, const char *cach
     if (!dl) { if (log) *log = dup_cstr(std::string("dlopen failed: ") + dlerror() + "\n"); return nullptr; }
     drs_kernel *k = new drs_kernel();
     k->dl = dl;
-    k->launch = (int (*)(const void *, void *, hipStream_t))dlsym(dl, "drs_plugin_launch");
-    k->launch_gold = (int (*)(const void *, void *, hipStream_t))dlsym(dl, "drs_plugin_launch_gold");
-    k->launch_pair = (int (*)(const void *, void *, const void *, void *, hipStream_t))dlsym(dl, "drs_plugin_launch_pair");
-    k->launch_src = (int (*)(const void *, void *, const void *, hipStream_t))dlsym(dl, "drs_plugin_launch_src");
-    k->launch_gold_src = (int (*)(const void *, void *, const void *, hipStream_t))dlsym(dl, "drs_plugin_launch_gold_src");
-    k->launch_res = (int (*)(const void *, void *, const void *, void *, hipStream_t))dlsym(dl, "drs_plugin_launch_res");
-    k->launch_fix = (int (*)(const void *, void *, const void *, void *, const void *, hipStream_t))dlsym(dl, "drs_plugin_launch_fix");
-    k->launch_gold_fix = (int (*)(const void *, void *, const void *, const void *, hipStream_t))dlsym(dl, "drs_plugin_launch_gold_fix");
-    k->launch_ops = (int (*)(const void *, void *, const void *, void *, const void *, const void *, hipStream_t))dlsym(dl, "drs_plugin_launch_ops");
-    k->launch_gold_ops = (int (*)(const void *, void *, const void *, const void *, const void *, hipStream_t))dlsym(dl, "drs_plugin_launch_gold_ops");
-    k->has_source = r.plan.source;
-    k->has_fix = r.plan.dirichlet;
-    k->has_scale = r.plan.scale;
-    k->has_coef = r.plan.varcoef;
-    if (k->has_coef) {
-        k->launch_opsk = (decltype(k->launch_opsk))(void *)k->launch_ops;
-        k->launch_gold_opsk = (decltype(k->launch_gold_opsk))(void *)k->launch_gold_ops;
+    k->abi = LaunchAbi(r.plan, r.opt.pair_launch != 0);
+    k->sweep = dlsym(dl, k->abi.sweep_symbol().c_str());
+    k->gold = dlsym(dl, k->abi.gold_symbol().c_str());
+    if (k->abi.sweep == LaunchAbi::PLAIN) k->launch = (decltype(k->launch))k->sweep;
+    k->launch_pair = (decltype(k->launch_pair))dlsym(dl, "drs_plugin_launch_pair");
+    k->wrap = (decltype(k->wrap))dlsym(dl, "drs_plugin_wrap");
+    k->info = (decltype(k->info))dlsym(dl, "drs_plugin_info");
+    if (k->abi.takes[SLOT_COEF]) {
         for (auto &t : r.plan.taps) {
             const int kk = r.plan.ndim == 3 ? t.ds : 0, jj = r.plan.ndim == 3 ? t.dy : r.plan.has_y ? t.dy : t.ds;
             k->coef_taps += (k->coef_taps.empty() ? "[[" : ",[") + std::to_string(kk) + "," + std::to_string(jj) + "," + std::to_string(t.dx) + "]";
@@ -379,27 +357,19 @@ drs_kernel *drs_kernel_build(int argc, const char *const *argv, const char *cach
     }
     k->fp32 = r.plan.fp32;
     k->residual_elems = r.plan.residual ? Schedule(r.plan, r.opt).residual_elems() : 0;
-    k->wrap = (int (*)(void *, hipStream_t))dlsym(dl, "drs_plugin_wrap");
-    k->info = (const char *(*)(void))dlsym(dl, "drs_plugin_info");
     k->path = so;
     k->resources = resources;
     k->step = r.st.step;
     k->horizon = r.plan.reassociated ? r.plan.horizon_iterations : -1;
     k->forced = r.plan.temporal_forced;
-    // either set of launch entry points, whole: the two-pointer one, or (--source) the three-pointer one; with --residual the sweep's entry
-    // point of either set gives way to drs_plugin_launch_res and the gold one stays
-    const bool with_res = r.plan.residual;
-    const bool sweep_plain = with_res ? (k->launch_res && !k->launch && !k->launch_src) : (k->launch && !k->launch_src && !k->launch_res);
-    const bool sweep_src = with_res ? sweep_plain : (k->launch_src && !k->launch && !k->launch_res);
-    const bool plain = sweep_plain && k->launch_gold && !k->launch_gold_src;
-    const bool with_src = sweep_src && k->launch_gold_src && !k->launch_gold;
-    // --dirichlet: its two entry points and none of the others
-    const bool others = k->launch || k->launch_gold || k->launch_src || k->launch_gold_src || k->launch_res;
-    const bool with_fix = k->launch_fix && k->launch_gold_fix && !others;
-    // --scale: its two entry points and none of the others, --dirichlet's included
-    const bool with_ops = k->launch_ops && k->launch_gold_ops && !others && !k->launch_fix && !k->launch_gold_fix;
-    const bool fix_ok = (r.plan.scale || r.plan.varcoef) ? with_ops : (!k->launch_ops && !k->launch_gold_ops && (r.plan.dirichlet ? with_fix : (!k->launch_fix && !k->launch_gold_fix)));
-    if (!fix_ok || (!r.plan.dirichlet && !r.plan.scale && !r.plan.varcoef && (!(plain || with_src) || with_src != r.plan.source)) || !k->info) {
+    // the plugin exports the two launch entry points its plan names and those of no other family
+    bool whole = k->sweep && k->gold && k->info;
+    for (int f = LaunchAbi::PLAIN; f <= LaunchAbi::OPS; f++)
+        for (const char *stem : {"drs_plugin_launch", "drs_plugin_launch_gold"}) {
+            const std::string name = std::string(stem) + LaunchAbi::suffix((LaunchAbi::Family)f);
+            whole = whole && (dlsym(dl, name.c_str()) != nullptr) == (name == k->abi.sweep_symbol() || name == k->abi.gold_symbol());
+        }
+    if (!whole) {
         if (log) *log = dup_cstr("plugin " + so + " lacks the drs_plugin_* entry points\n");
         dlclose(dl);
         delete k;
@@ -407,6 +377,7 @@ drs_kernel *drs_kernel_build(int argc, const char *const *argv, const char *cach
     }
     return k;
 }
+
 
 void drs_kernel_close(drs_kernel *k) {
     if (!k) return;
@@ -441,127 +412,84 @@ int drs_kernel_pair_layout(const drs_kernel *k, size_t *arena_bytes, size_t *out
     return 0;
 }
 
-int drs_kernel_launch(drs_kernel *k, const void *d_in, void *d_out, void *stream) {
-    if (!k->launch) return -2;           // a --source kernel: drs_kernel_launch_src
-    g_launched = true;
-    return k->launch(d_in, d_out, (hipStream_t)stream);
-}
-int drs_kernel_launch_pair(drs_kernel *k, const void *d_in0, void *d_out0, const void *d_in1, void *d_out1, void *stream) {
-    if (!k->launch_pair) return -2;      // the kernel was not generated with --pair-launch 1
-    g_launched = true;
-    return k->launch_pair(d_in0, d_out0, d_in1, d_out1, (hipStream_t)stream);
-}
-int drs_kernel_wrap(drs_kernel *k, void *d, void *stream) {
-    if (!k->wrap) return -2;             // the kernel fills no ring: every axis is fixed
-    g_launched = true;
-    return k->wrap(d, (hipStream_t)stream);
-}
-int drs_kernel_launch_gold(drs_kernel *k, const void *d_in, void *d_out, void *stream) {
-    if (!k->launch_gold) return -2;      // a --source kernel: drs_kernel_launch_gold_src
-    g_launched = true;
-    return k->launch_gold(d_in, d_out, (hipStream_t)stream);
-}
-int drs_kernel_launch_src(drs_kernel *k, const void *d_in, void *d_out, const void *d_src, void *stream) {
-    if (!k->launch_src || !d_src) return -2;      // the kernel was not generated with --source, or no source array
-    g_launched = true;
-    return k->launch_src(d_in, d_out, d_src, (hipStream_t)stream);
-}
-int drs_kernel_launch_gold_src(drs_kernel *k, const void *d_in, void *d_out, const void *d_src, void *stream) {
-    if (!k->launch_gold_src || !d_src) return -2;
-    g_launched = true;
-    return k->launch_gold_src(d_in, d_out, d_src, (hipStream_t)stream);
-}
-
 long drs_kernel_residual_elems(const drs_kernel *k) { return k ? k->residual_elems : 0; }
-// the source array of a --residual call, checked against the kernel: a --source kernel needs one, a kernel without it takes none
-static bool res_args_ok(const drs_kernel *k, const void *d_src, const void *d_res) { return k->launch_res && d_res && (k->has_source ? d_src != nullptr : d_src == nullptr); }
-int drs_kernel_launch_res(drs_kernel *k, const void *d_in, void *d_out, const void *d_src, void *d_res, void *stream) {
-    if (!res_args_ok(k, d_src, d_res)) return -2;      // the kernel was not generated with --residual, no residual array, or a source array that does not go with the kernel
-    g_launched = true;
-    return k->launch_res(d_in, d_out, d_src, d_res, (hipStream_t)stream);
-}
+const char *drs_kernel_coef_taps(const drs_kernel *k) { return (k && k->abi.takes[SLOT_COEF]) ? k->coef_taps.c_str() : nullptr; }
 
-// the ping-pong loop of both forms: d_src == nullptr on a kernel without --source, the source array of every launch on one with it
-static int run_loop(drs_kernel *k, void *d_a, void *d_b, const void *d_src, int iterations, int gold, void *stream) {
-    // a temporal pipeline is only offered where it keeps the tolerance: more iterations than its horizon need the fused kernel
-    // (or --temporal force, whose plugin says "temporal_forced" in drs_kernel_info)
-    if (!gold && k->horizon >= 0 && !k->forced && iterations > k->horizon) return -3;
-    auto fn = gold ? k->launch_gold : k->launch;
-    auto fn_src = gold ? k->launch_gold_src : k->launch_src;
-    auto one = [&](const void *in, void *out) { return d_src ? fn_src(in, out, d_src, (hipStream_t)stream) : fn(in, out, (hipStream_t)stream); };
+// ---- the one launch path.  Every family of entry points below -- plain, _src, _res, _fix and _ops -- checks what it accepts, fills an
+// Operands and calls these; a call that is refused (-2, -3) has launched nothing and leaves g_launched alone ---------------------------------
+namespace {
+struct Operands { const void *p[NSLOTS] = {}; };      // the arrays of a launch beside in and out, by slot (plan.hpp); null: none
+// every array the kernel takes is there and no other is.  The gold kernel computes no residual: a gold form leaves res alone and takes one
+// only on a --residual max kernel
+bool operands_ok(const drs_kernel *k, const Operands &v, bool gold) {
+    for (int i = 0; i < NSLOTS; i++) {
+        const bool given = v.p[i] != nullptr, taken = k->abi.takes[i];
+        if (gold && i == SLOT_RES ? (given && !taken) : given != taken) return false;
+    }
+    return true;
+}
+// a suffixed family accepts a kernel exactly when its plugin exports that family's symbol, with the arrays that go with the kernel
+bool family_ok(const drs_kernel *k, LaunchAbi::Family f, const Operands &v, bool gold = false) {
+    return (gold ? k->abi.gold : k->abi.sweep) == f && operands_ok(k, v, gold);
+}
+// the operand block of the _ops family: any kernel, a block of the right size
+bool block_ok(const drs_kernel *k, const drs_operands *ops, bool gold, Operands &v) {
+    if (!k || !ops || ops->size != sizeof(drs_operands)) return false;
+    v = Operands{{ops->src, ops->res, ops->fix, ops->scale, ops->coef}};
+    return operands_ok(k, v, gold);
+}
+// One launch through the plugin's sweep or gold entry point: (in, out, the slots of its signature, stream), every parameter a pointer (a C
+// symbol from dlsym: called by the number of its pointers, two to seven)
+int launch_one(const drs_kernel *k, const void *in, void *out, const Operands &v, bool gold, hipStream_t s) {
+    using P = const void *;
+    P a[2 + NSLOTS] = {in, out};
+    int n = 2;
+    for (int i = 0; i < NSLOTS; i++)
+        if (k->abi.in_signature(i, gold)) a[n++] = v.p[i];
+    void *f = gold ? k->gold : k->sweep;
+    switch (n) {
+    case 2: return ((int (*)(P, P, hipStream_t))f)(a[0], a[1], s);
+    case 3: return ((int (*)(P, P, P, hipStream_t))f)(a[0], a[1], a[2], s);
+    case 4: return ((int (*)(P, P, P, P, hipStream_t))f)(a[0], a[1], a[2], a[3], s);
+    case 5: return ((int (*)(P, P, P, P, P, hipStream_t))f)(a[0], a[1], a[2], a[3], a[4], s);
+    case 6: return ((int (*)(P, P, P, P, P, P, hipStream_t))f)(a[0], a[1], a[2], a[3], a[4], a[5], s);
+    default: return ((int (*)(P, P, P, P, P, P, P, hipStream_t))f)(a[0], a[1], a[2], a[3], a[4], a[5], a[6], s);
+    }
+}
+int launch(drs_kernel *k, const void *in, void *out, const Operands &v, bool gold, void *stream) {
+    g_launched = true;
+    return launch_one(k, in, out, v, gold, (hipStream_t)stream);
+}
+// the reference's ping-pong loop, the same arrays in every launch: the launches made, or -1
+int ping_pong(drs_kernel *k, void *d_a, void *d_b, const Operands &v, int iterations, bool gold, hipStream_t s) {
     g_launched = true;
     int n = 0;
     for (int t = 0; t < iterations; t += 2 * k->step) {
-        if (one(d_a, d_b) != 0) return -1;
-        if (one(d_b, d_a) != 0) return -1;
+        if (launch_one(k, d_a, d_b, v, gold, s) != 0) return -1;
+        if (launch_one(k, d_b, d_a, v, gold, s) != 0) return -1;
         n += 2;
     }
     return n;
 }
-
-static int run_timed_loop(drs_kernel *k, void *d_a, void *d_b, const void *d_src, int iterations, int warmup, void *stream, float *ms) {
+// A temporal pipeline is only offered where it keeps the tolerance: more iterations than its horizon need the fused kernel (or --temporal
+// force, whose plugin says "temporal_forced" in drs_kernel_info).  Asked of every family alike: the planner refuses --temporal with
+// --residual max and with --dirichlet (planner.hpp: make_plan), so the kernels drs_kernel_run_res and _run_fix accept have no horizon (-1)
+bool beyond_horizon(const drs_kernel *k, int iterations) { return k->horizon >= 0 && !k->forced && iterations > k->horizon; }
+int run(drs_kernel *k, void *d_a, void *d_b, const Operands &v, int iterations, bool gold, void *stream) {
+    if (!gold && beyond_horizon(k, iterations)) return -3;
+    return ping_pong(k, d_a, d_b, v, iterations, gold, (hipStream_t)stream);
+}
+// `warmup` launches (A,B), then the loop between two events on the stream
+int run_timed(drs_kernel *k, void *d_a, void *d_b, const Operands &v, int iterations, int warmup, void *stream, float *ms) {
     hipStream_t s = (hipStream_t)stream;
-    if (k->horizon >= 0 && !k->forced && iterations > k->horizon) return -3;      // as drs_kernel_run, before anything is launched
+    if (beyond_horizon(k, iterations)) return -3;      // before anything is launched
     g_launched = true;
     for (int i = 0; i < warmup; i++)
-        if ((d_src ? k->launch_src(d_a, d_b, d_src, s) : k->launch(d_a, d_b, s)) != 0) return -1;
+        if (launch_one(k, d_a, d_b, v, false, s) != 0) return -1;
     hipEvent_t e0, e1;
     if (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess) return -1;
     (void)hipEventRecord(e0, s);
-    int n = run_loop(k, d_a, d_b, d_src, iterations, 0, stream);
-    (void)hipEventRecord(e1, s);
-    hipError_t err = hipEventSynchronize(e1);
-    float t = 0.f;
-    if (err == hipSuccess) err = hipEventElapsedTime(&t, e0, e1);
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
-    if (ms) *ms = t;
-    return (err == hipSuccess) ? n : -1;
-}
-
-int drs_kernel_run(drs_kernel *k, void *d_a, void *d_b, int iterations, int gold, void *stream) {
-    if (!k->launch) return -2;           // a --source kernel: drs_kernel_run_src
-    return run_loop(k, d_a, d_b, nullptr, iterations, gold, stream);
-}
-int drs_kernel_run_src(drs_kernel *k, void *d_a, void *d_b, const void *d_src, int iterations, int gold, void *stream) {
-    if (!k->launch_src || !d_src) return -2;
-    return run_loop(k, d_a, d_b, d_src, iterations, gold, stream);
-}
-
-int drs_kernel_run_timed(drs_kernel *k, void *d_a, void *d_b, int iterations, int warmup, void *stream, float *ms) {
-    if (!k->launch) return -2;           // a --source kernel: drs_kernel_run_timed_src
-    return run_timed_loop(k, d_a, d_b, nullptr, iterations, warmup, stream, ms);
-}
-int drs_kernel_run_timed_src(drs_kernel *k, void *d_a, void *d_b, const void *d_src, int iterations, int warmup, void *stream, float *ms) {
-    if (!k->launch_src || !d_src) return -2;
-    return run_timed_loop(k, d_a, d_b, d_src, iterations, warmup, stream, ms);
-}
-
-// ---- --residual kernels: the loops with the residual array, and the run to tolerance -----------------------------------------------------
-static int run_loop_res(drs_kernel *k, void *d_a, void *d_b, const void *d_src, void *d_res, int iterations, void *stream) {
-    g_launched = true;
-    int n = 0;
-    for (int t = 0; t < iterations; t += 2 * k->step) {
-        if (k->launch_res(d_a, d_b, d_src, d_res, (hipStream_t)stream) != 0) return -1;
-        if (k->launch_res(d_b, d_a, d_src, d_res, (hipStream_t)stream) != 0) return -1;
-        n += 2;
-    }
-    return n;
-}
-int drs_kernel_run_res(drs_kernel *k, void *d_a, void *d_b, const void *d_src, void *d_res, int iterations, void *stream) {
-    if (!res_args_ok(k, d_src, d_res)) return -2;
-    return run_loop_res(k, d_a, d_b, d_src, d_res, iterations, stream);
-}
-int drs_kernel_run_timed_res(drs_kernel *k, void *d_a, void *d_b, const void *d_src, void *d_res, int iterations, int warmup, void *stream, float *ms) {
-    if (!res_args_ok(k, d_src, d_res)) return -2;
-    hipStream_t s = (hipStream_t)stream;
-    g_launched = true;
-    for (int i = 0; i < warmup; i++)
-        if (k->launch_res(d_a, d_b, d_src, d_res, s) != 0) return -1;
-    hipEvent_t e0, e1;
-    if (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess) return -1;
-    (void)hipEventRecord(e0, s);
-    const int n = run_loop_res(k, d_a, d_b, d_src, d_res, iterations, stream);
+    const int n = ping_pong(k, d_a, d_b, v, iterations, false, s);
     (void)hipEventRecord(e1, s);
     hipError_t err = hipEventSynchronize(e1);
     float t = 0.f;
@@ -572,212 +500,149 @@ int drs_kernel_run_timed_res(drs_kernel *k, void *d_a, void *d_b, const void *d_
     return (err == hipSuccess) ? n : -1;
 }
 // d_res[0] on the host, as a double (exact for either dtype); false on a HIP error
-static bool read_residual(const drs_kernel *k, const void *d_res, double *r) {
+bool read_residual(const drs_kernel *k, const void *d_res, double *r) {
     if (k->fp32) { float v = 0.f; if (hipMemcpy(&v, d_res, sizeof v, hipMemcpyDeviceToHost) != hipSuccess) return false; *r = (double)v; }
     else if (hipMemcpy(r, d_res, sizeof *r, hipMemcpyDeviceToHost) != hipSuccess) return false;
     return true;
+}
+// the run to tolerance; `accepted`: the caller's family takes the kernel with these arrays (-2 also without --residual max)
+int solve(drs_kernel *k, bool accepted, void *d_a, void *d_b, const Operands &v, double tol, int max_launches, int check_every_pairs, void *stream, int *launches,
+          double *residual) {
+    if (launches) *launches = 0;
+    if (residual) *residual = std::nan("");
+    if (!accepted || !k->residual_elems || check_every_pairs < 1) return -2;
+    const int limit = max_launches < 0 ? 0 : max_launches - max_launches % 2;
+    int n = 0;
+    double r = std::nan("");
+    g_launched = true;
+    while (n < limit) {
+        const int pairs = std::min(check_every_pairs, (limit - n) / 2);
+        if (ping_pong(k, d_a, d_b, v, 2 * pairs * k->step, false, (hipStream_t)stream) != 2 * pairs) return -1;
+        n += 2 * pairs;
+        if (hipStreamSynchronize((hipStream_t)stream) != hipSuccess || !read_residual(k, v.p[SLOT_RES], &r)) return -1;
+        if (launches) *launches = n;
+        if (residual) *residual = r;
+        if (std::isnan(r) || std::isinf(r)) return -4;       // diverged or overflowed: reported, not iterated on
+        if (r <= tol) return 0;
+    }
+    return 1;
+}
+}  // namespace
+
+int drs_kernel_launch_pair(drs_kernel *k, const void *d_in0, void *d_out0, const void *d_in1, void *d_out1, void *stream) {
+    if (!k->launch_pair) return -2;      // the kernel was not generated with --pair-launch 1
+    g_launched = true;
+    return k->launch_pair(d_in0, d_out0, d_in1, d_out1, (hipStream_t)stream);
+}
+int drs_kernel_wrap(drs_kernel *k, void *d, void *stream) {
+    if (!k->wrap) return -2;             // the kernel fills no ring: every axis is fixed
+    g_launched = true;
+    return k->wrap(d, (hipStream_t)stream);
 }
 int drs_kernel_residual(const drs_kernel *k, const void *d_res, double *r) {
     if (!k->residual_elems || !d_res || !r) return -2;
     return read_residual(k, d_res, r) ? 0 : -1;
 }
+
+// ---- the plain family: kernels whose plugin exports drs_plugin_launch / drs_plugin_launch_gold (the latter also with --residual max alone)
+int drs_kernel_launch(drs_kernel *k, const void *d_in, void *d_out, void *stream) {
+    return family_ok(k, LaunchAbi::PLAIN, {}) ? launch(k, d_in, d_out, {}, false, stream) : -2;
+}
+int drs_kernel_launch_gold(drs_kernel *k, const void *d_in, void *d_out, void *stream) {
+    return family_ok(k, LaunchAbi::PLAIN, {}, true) ? launch(k, d_in, d_out, {}, true, stream) : -2;
+}
+int drs_kernel_run(drs_kernel *k, void *d_a, void *d_b, int iterations, int gold, void *stream) {
+    return family_ok(k, LaunchAbi::PLAIN, {}) ? run(k, d_a, d_b, {}, iterations, gold != 0, stream) : -2;
+}
+int drs_kernel_run_timed(drs_kernel *k, void *d_a, void *d_b, int iterations, int warmup, void *stream, float *ms) {
+    return family_ok(k, LaunchAbi::PLAIN, {}) ? run_timed(k, d_a, d_b, {}, iterations, warmup, stream, ms) : -2;
+}
+
+// ---- the _src family: --source kernels; -2 also on a null d_src
+int drs_kernel_launch_src(drs_kernel *k, const void *d_in, void *d_out, const void *d_src, void *stream) {
+    const Operands v{{d_src}};
+    return family_ok(k, LaunchAbi::SRC, v) ? launch(k, d_in, d_out, v, false, stream) : -2;
+}
+int drs_kernel_launch_gold_src(drs_kernel *k, const void *d_in, void *d_out, const void *d_src, void *stream) {
+    const Operands v{{d_src}};
+    return family_ok(k, LaunchAbi::SRC, v, true) ? launch(k, d_in, d_out, v, true, stream) : -2;
+}
+int drs_kernel_run_src(drs_kernel *k, void *d_a, void *d_b, const void *d_src, int iterations, int gold, void *stream) {
+    const Operands v{{d_src}};
+    return family_ok(k, LaunchAbi::SRC, v) ? run(k, d_a, d_b, v, iterations, gold != 0, stream) : -2;
+}
+int drs_kernel_run_timed_src(drs_kernel *k, void *d_a, void *d_b, const void *d_src, int iterations, int warmup, void *stream, float *ms) {
+    const Operands v{{d_src}};
+    return family_ok(k, LaunchAbi::SRC, v) ? run_timed(k, d_a, d_b, v, iterations, warmup, stream, ms) : -2;
+}
+
+// ---- the _res family: --residual max kernels; -2 also on a null d_res and on a d_src that does not go with the kernel (null exactly
+// without --source)
+int drs_kernel_launch_res(drs_kernel *k, const void *d_in, void *d_out, const void *d_src, void *d_res, void *stream) {
+    const Operands v{{d_src, d_res}};
+    return family_ok(k, LaunchAbi::RES, v) ? launch(k, d_in, d_out, v, false, stream) : -2;
+}
+int drs_kernel_run_res(drs_kernel *k, void *d_a, void *d_b, const void *d_src, void *d_res, int iterations, void *stream) {
+    const Operands v{{d_src, d_res}};
+    return family_ok(k, LaunchAbi::RES, v) ? run(k, d_a, d_b, v, iterations, false, stream) : -2;
+}
+int drs_kernel_run_timed_res(drs_kernel *k, void *d_a, void *d_b, const void *d_src, void *d_res, int iterations, int warmup, void *stream, float *ms) {
+    const Operands v{{d_src, d_res}};
+    return family_ok(k, LaunchAbi::RES, v) ? run_timed(k, d_a, d_b, v, iterations, warmup, stream, ms) : -2;
+}
 int drs_kernel_solve(drs_kernel *k, void *d_a, void *d_b, const void *d_src, void *d_res, double tol, int max_launches, int check_every_pairs, void *stream,
                      int *launches, double *residual) {
-    if (launches) *launches = 0;
-    if (residual) *residual = std::nan("");
-    if (!res_args_ok(k, d_src, d_res) || check_every_pairs < 1) return -2;
-    const int limit = max_launches < 0 ? 0 : max_launches - max_launches % 2;
-    int n = 0;
-    double r = std::nan("");
-    g_launched = true;
-    while (n < limit) {
-        const int pairs = std::min(check_every_pairs, (limit - n) / 2);
-        for (int i = 0; i < pairs; i++) {
-            if (k->launch_res(d_a, d_b, d_src, d_res, (hipStream_t)stream) != 0) return -1;
-            if (k->launch_res(d_b, d_a, d_src, d_res, (hipStream_t)stream) != 0) return -1;
-        }
-        n += 2 * pairs;
-        if (hipStreamSynchronize((hipStream_t)stream) != hipSuccess || !read_residual(k, d_res, &r)) return -1;
-        if (launches) *launches = n;
-        if (residual) *residual = r;
-        if (std::isnan(r) || std::isinf(r)) return -4;       // diverged or overflowed: reported, not iterated on
-        if (r <= tol) return 0;
-    }
-    return 1;
+    const Operands v{{d_src, d_res}};
+    return solve(k, family_ok(k, LaunchAbi::RES, v), d_a, d_b, v, tol, max_launches, check_every_pairs, stream, launches, residual);
 }
 
-// ---- --dirichlet kernels: held cells.  Every array in every signature: d_src / d_res are null exactly when the kernel was generated without
-// --source / --residual max; d_fix is never null -------------------------------------------------------------------------------------------
-static bool fix_args_ok(const drs_kernel *k, const void *d_src, const void *d_res, const void *d_fix) {
-    return k->launch_fix && d_fix && (k->has_source ? d_src != nullptr : d_src == nullptr) && (k->residual_elems ? d_res != nullptr : d_res == nullptr);
-}
+// ---- the _fix family: --dirichlet kernels; -2 also on a null d_fix and on a d_src / d_res that does not go with the kernel (null exactly
+// without --source / --residual max; the run's gold form asks the same of d_res and leaves it alone)
 int drs_kernel_launch_fix(drs_kernel *k, const void *d_in, void *d_out, const void *d_src, void *d_res, const void *d_fix, void *stream) {
-    if (!fix_args_ok(k, d_src, d_res, d_fix)) return -2;      // the kernel was not generated with --dirichlet, no fix array, or a src / res array that does not go with the kernel
-    g_launched = true;
-    return k->launch_fix(d_in, d_out, d_src, d_res, d_fix, (hipStream_t)stream);
+    const Operands v{{d_src, d_res, d_fix}};
+    return family_ok(k, LaunchAbi::FIX, v) ? launch(k, d_in, d_out, v, false, stream) : -2;
 }
 int drs_kernel_launch_gold_fix(drs_kernel *k, const void *d_in, void *d_out, const void *d_src, const void *d_fix, void *stream) {
-    if (!k->launch_gold_fix || !d_fix || (k->has_source ? d_src == nullptr : d_src != nullptr)) return -2;
-    g_launched = true;
-    return k->launch_gold_fix(d_in, d_out, d_src, d_fix, (hipStream_t)stream);
-}
-static int run_loop_fix(drs_kernel *k, void *d_a, void *d_b, const void *d_src, void *d_res, const void *d_fix, int iterations, int gold, void *stream) {
-    auto one = [&](const void *in, void *out) {
-        return gold ? k->launch_gold_fix(in, out, d_src, d_fix, (hipStream_t)stream) : k->launch_fix(in, out, d_src, d_res, d_fix, (hipStream_t)stream);
-    };
-    g_launched = true;
-    int n = 0;
-    for (int t = 0; t < iterations; t += 2 * k->step) {      // step is 1: --dirichlet refuses a fused launch
-        if (one(d_a, d_b) != 0) return -1;
-        if (one(d_b, d_a) != 0) return -1;
-        n += 2;
-    }
-    return n;
+    const Operands v{{d_src, nullptr, d_fix}};
+    return family_ok(k, LaunchAbi::FIX, v, true) ? launch(k, d_in, d_out, v, true, stream) : -2;
 }
 int drs_kernel_run_fix(drs_kernel *k, void *d_a, void *d_b, const void *d_src, void *d_res, const void *d_fix, int iterations, int gold, void *stream) {
-    if (!fix_args_ok(k, d_src, d_res, d_fix)) return -2;
-    return run_loop_fix(k, d_a, d_b, d_src, d_res, d_fix, iterations, gold, stream);
+    const Operands v{{d_src, d_res, d_fix}};
+    return family_ok(k, LaunchAbi::FIX, v) ? run(k, d_a, d_b, v, iterations, gold != 0, stream) : -2;
 }
 int drs_kernel_run_timed_fix(drs_kernel *k, void *d_a, void *d_b, const void *d_src, void *d_res, const void *d_fix, int iterations, int warmup, void *stream, float *ms) {
-    if (!fix_args_ok(k, d_src, d_res, d_fix)) return -2;
-    hipStream_t s = (hipStream_t)stream;
-    g_launched = true;
-    for (int i = 0; i < warmup; i++)
-        if (k->launch_fix(d_a, d_b, d_src, d_res, d_fix, s) != 0) return -1;
-    hipEvent_t e0, e1;
-    if (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess) return -1;
-    (void)hipEventRecord(e0, s);
-    const int n = run_loop_fix(k, d_a, d_b, d_src, d_res, d_fix, iterations, 0, stream);
-    (void)hipEventRecord(e1, s);
-    hipError_t err = hipEventSynchronize(e1);
-    float t = 0.f;
-    if (err == hipSuccess) err = hipEventElapsedTime(&t, e0, e1);
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
-    if (ms) *ms = t;
-    return (err == hipSuccess) ? n : -1;
+    const Operands v{{d_src, d_res, d_fix}};
+    return family_ok(k, LaunchAbi::FIX, v) ? run_timed(k, d_a, d_b, v, iterations, warmup, stream, ms) : -2;
 }
-// drs_kernel_solve with held cells: the same loop, the same answers; needs --residual max as well
 int drs_kernel_solve_fix(drs_kernel *k, void *d_a, void *d_b, const void *d_src, void *d_res, const void *d_fix, double tol, int max_launches, int check_every_pairs,
                          void *stream, int *launches, double *residual) {
-    if (launches) *launches = 0;
-    if (residual) *residual = std::nan("");
-    if (!fix_args_ok(k, d_src, d_res, d_fix) || !k->residual_elems || check_every_pairs < 1) return -2;
-    const int limit = max_launches < 0 ? 0 : max_launches - max_launches % 2;
-    int n = 0;
-    double r = std::nan("");
-    g_launched = true;
-    while (n < limit) {
-        const int pairs = std::min(check_every_pairs, (limit - n) / 2);
-        for (int i = 0; i < pairs; i++) {
-            if (k->launch_fix(d_a, d_b, d_src, d_res, d_fix, (hipStream_t)stream) != 0) return -1;
-            if (k->launch_fix(d_b, d_a, d_src, d_res, d_fix, (hipStream_t)stream) != 0) return -1;
-        }
-        n += 2 * pairs;
-        if (hipStreamSynchronize((hipStream_t)stream) != hipSuccess || !read_residual(k, d_res, &r)) return -1;
-        if (launches) *launches = n;
-        if (residual) *residual = r;
-        if (std::isnan(r) || std::isinf(r)) return -4;       // diverged or overflowed: reported, not iterated on
-        if (r <= tol) return 0;
-    }
-    return 1;
+    const Operands v{{d_src, d_res, d_fix}};
+    return solve(k, family_ok(k, LaunchAbi::FIX, v), d_a, d_b, v, tol, max_launches, check_every_pairs, stream, launches, residual);
 }
 
-// ---- the operand block: one family of entry points for every kernel, whatever arrays it takes ----------------------------------------------
-// ops->size is checked; a pointer the kernel needs must be non-null and a pointer it does not take must be null, else -2 (the gold kernel
-// computes no residual: the gold forms leave ops->res alone, and take it only on a --residual max kernel)
-namespace {
-struct Operands { const void *src = nullptr; void *res = nullptr; const void *fix = nullptr; const void *scale = nullptr; const void *coef = nullptr; };
-bool ops_ok(const drs_kernel *k, const drs_operands *ops, bool gold, Operands &v) {
-    if (!k || !ops || ops->size != sizeof(drs_operands)) return false;
-    v.src = ops->src; v.res = ops->res; v.fix = ops->fix; v.scale = ops->scale; v.coef = ops->coef;
-    if ((v.src != nullptr) != k->has_source || (v.fix != nullptr) != k->has_fix || (v.scale != nullptr) != k->has_scale || (v.coef != nullptr) != k->has_coef) return false;
-    if (gold) return k->residual_elems ? true : v.res == nullptr;
-    return (v.res != nullptr) == (k->residual_elems != 0);
-}
-// one launch through whichever entry points the plugin exports
-int ops_one(drs_kernel *k, const void *in, void *out, const Operands &v, bool gold, hipStream_t s) {
-    if (k->has_coef) return gold ? k->launch_gold_opsk(in, out, v.src, v.fix, v.scale, v.coef, s) : k->launch_opsk(in, out, v.src, v.res, v.fix, v.scale, v.coef, s);
-    if (k->has_scale) return gold ? k->launch_gold_ops(in, out, v.src, v.fix, v.scale, s) : k->launch_ops(in, out, v.src, v.res, v.fix, v.scale, s);
-    if (k->has_fix) return gold ? k->launch_gold_fix(in, out, v.src, v.fix, s) : k->launch_fix(in, out, v.src, v.res, v.fix, s);
-    if (gold) return v.src ? k->launch_gold_src(in, out, v.src, s) : k->launch_gold(in, out, s);
-    if (k->residual_elems) return k->launch_res(in, out, v.src, v.res, s);
-    return v.src ? k->launch_src(in, out, v.src, s) : k->launch(in, out, s);
-}
-int ops_loop(drs_kernel *k, void *d_a, void *d_b, const Operands &v, int iterations, bool gold, hipStream_t s) {
-    g_launched = true;
-    int n = 0;
-    for (int t = 0; t < iterations; t += 2 * k->step) {
-        if (ops_one(k, d_a, d_b, v, gold, s) != 0) return -1;
-        if (ops_one(k, d_b, d_a, v, gold, s) != 0) return -1;
-        n += 2;
-    }
-    return n;
-}
-}  // namespace
-const char *drs_kernel_coef_taps(const drs_kernel *k) { return (k && k->has_coef) ? k->coef_taps.c_str() : nullptr; }
+// ---- the operand block: one family of entry points for every kernel, whatever arrays it takes; -2 also on a block of another size
 int drs_kernel_launch_ops(drs_kernel *k, const void *d_in, void *d_out, const drs_operands *ops, void *stream) {
     Operands v;
-    if (!ops_ok(k, ops, false, v)) return -2;
-    g_launched = true;
-    return ops_one(k, d_in, d_out, v, false, (hipStream_t)stream);
+    return block_ok(k, ops, false, v) ? launch(k, d_in, d_out, v, false, stream) : -2;
 }
 int drs_kernel_launch_gold_ops(drs_kernel *k, const void *d_in, void *d_out, const drs_operands *ops, void *stream) {
     Operands v;
-    if (!ops_ok(k, ops, true, v)) return -2;
-    g_launched = true;
-    return ops_one(k, d_in, d_out, v, true, (hipStream_t)stream);
+    return block_ok(k, ops, true, v) ? launch(k, d_in, d_out, v, true, stream) : -2;
 }
 int drs_kernel_run_ops(drs_kernel *k, void *d_a, void *d_b, const drs_operands *ops, int iterations, int gold, void *stream) {
     Operands v;
-    if (!ops_ok(k, ops, gold != 0, v)) return -2;
-    if (!gold && k->horizon >= 0 && !k->forced && iterations > k->horizon) return -3;      // as drs_kernel_run
-    return ops_loop(k, d_a, d_b, v, iterations, gold != 0, (hipStream_t)stream);
+    return block_ok(k, ops, gold != 0, v) ? run(k, d_a, d_b, v, iterations, gold != 0, stream) : -2;
 }
 int drs_kernel_run_timed_ops(drs_kernel *k, void *d_a, void *d_b, const drs_operands *ops, int iterations, int warmup, void *stream, float *ms) {
     Operands v;
-    if (!ops_ok(k, ops, false, v)) return -2;
-    if (k->horizon >= 0 && !k->forced && iterations > k->horizon) return -3;
-    hipStream_t s = (hipStream_t)stream;
-    g_launched = true;
-    for (int i = 0; i < warmup; i++)
-        if (ops_one(k, d_a, d_b, v, false, s) != 0) return -1;
-    hipEvent_t e0, e1;
-    if (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess) return -1;
-    (void)hipEventRecord(e0, s);
-    const int n = ops_loop(k, d_a, d_b, v, iterations, false, s);
-    (void)hipEventRecord(e1, s);
-    hipError_t err = hipEventSynchronize(e1);
-    float t = 0.f;
-    if (err == hipSuccess) err = hipEventElapsedTime(&t, e0, e1);
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
-    if (ms) *ms = t;
-    return (err == hipSuccess) ? n : -1;
+    return block_ok(k, ops, false, v) ? run_timed(k, d_a, d_b, v, iterations, warmup, stream, ms) : -2;
 }
-// drs_kernel_solve through the operand block: the same loop, the same answers; -2 also on a kernel without --residual max
 int drs_kernel_solve_ops(drs_kernel *k, void *d_a, void *d_b, const drs_operands *ops, double tol, int max_launches, int check_every_pairs, void *stream,
                          int *launches, double *residual) {
-    if (launches) *launches = 0;
-    if (residual) *residual = std::nan("");
     Operands v;
-    if (!ops_ok(k, ops, false, v) || !k->residual_elems || check_every_pairs < 1) return -2;
-    const int limit = max_launches < 0 ? 0 : max_launches - max_launches % 2;
-    int n = 0;
-    double r = std::nan("");
-    g_launched = true;
-    while (n < limit) {
-        const int pairs = std::min(check_every_pairs, (limit - n) / 2);
-        if (ops_loop(k, d_a, d_b, v, 2 * pairs * k->step, false, (hipStream_t)stream) != 2 * pairs) return -1;
-        n += 2 * pairs;
-        if (hipStreamSynchronize((hipStream_t)stream) != hipSuccess || !read_residual(k, v.res, &r)) return -1;
-        if (launches) *launches = n;
-        if (residual) *residual = r;
-        if (std::isnan(r) || std::isinf(r)) return -4;       // diverged or overflowed: reported, not iterated on
-        if (r <= tol) return 0;
-    }
-    return 1;
+    return solve(k, block_ok(k, ops, false, v), d_a, d_b, v, tol, max_launches, check_every_pairs, stream, launches, residual);
 }
+
 
 // ---- inputs and error metric (common.hpp:9-102) -----------------------------------------------
 void drs_fill_random_f64(double *a, size_t n, unsigned seed) {

@@ -22,11 +22,26 @@ inline std::string check_call(const KernelPlan &p, const std::string &outer) {
     return p.ndim == 3 ? "checkError3D (M, N, " + outer + ", Halo, M-Halo, Halo, N-Halo)" : "checkError2D (N, " + outer + ", Halo, N-Halo)";
 }
 
+// ---- the launch interface (plan.hpp: LaunchAbi) as text.  res is the one array a launch writes
+inline std::string slot_type(int i, const char *elem) { return std::string(i == SLOT_RES ? "" : "const ") + elem + "*"; }
+// the arrays the kernel takes (the gold kernel: no res), as the tail of dr_<name>'s / gold_<name>'s parameter list ...
+inline std::string kernel_params(const LaunchAbi &abi, bool gold) {
+    std::string t;
+    for (int i = 0; i < NSLOTS; i++) if (abi.takes[i] && !(gold && i == SLOT_RES)) t += ", " + slot_type(i, "real_t") + " __restrict__ d_" + kSlotName[i];
+    return t;
+}
+// ... and as the tail of its argument list inside an entry point
+inline std::string kernel_args(const LaunchAbi &abi, bool gold) {
+    std::string t;
+    for (int i = 0; i < NSLOTS; i++) if (abi.takes[i] && !(gold && i == SLOT_RES)) t += ", (" + slot_type(i, "real_t") + ")" + kSlotName[i];
+    return t;
+}
+
 // ---- gold kernel (codegen.hpp:637-660): one lane per point, interior guard, same sum
 inline std::string gold_kernel(const KernelPlan &p) {
     std::ostringstream g;
     g << "// naive reference kernel: the verification arithmetic (same term order, same FMA chain)\n";
-    g << "extern \"C\" __global__ void gold_" << p.name << " (const real_t* __restrict__ d_in, real_t* __restrict__ d_out" << (p.source ? ", const real_t* __restrict__ d_src" : "") << (p.dirichlet ? ", const real_t* __restrict__ d_fix" : "") << (p.scale ? ", const real_t* __restrict__ d_scale" : "") << (p.varcoef ? ", const real_t* __restrict__ d_coef" : "") << ")\n{\n";
+    g << "extern \"C\" __global__ void gold_" << p.name << " (const real_t* __restrict__ d_in, real_t* __restrict__ d_out" << kernel_params(LaunchAbi(p), true) << ")\n{\n";
     g << "    const int i = (int)(blockIdx.x * blockDim.x + threadIdx.x);\n";
     g << "    const int j = (int)(blockIdx.y * blockDim.y + threadIdx.y);\n";
     if (p.ndim == 3) g << "    const int k = (int)(blockIdx.z * blockDim.z + threadIdx.z);\n";
@@ -205,9 +220,11 @@ inline std::string info_json(const Schedule &s) {
     return j;
 }
 
-// ---- plugin entry points (used when the source is built with -DDRS_PLUGIN -shared)
+// ---- plugin entry points (used when the source is built with -DDRS_PLUGIN -shared): the sweep's, the pair's with --pair-launch 1, the gold
+// kernel's and the info, with the names and signatures of the plan's LaunchAbi (plan.hpp)
 inline std::string plugin_api(const Schedule &s) {
     const KernelPlan &p = s.p; const GenOptions &o = s.o;
+    const LaunchAbi abi(p, o.pair_launch != 0);
     std::ostringstream a;
     a << "// ---- launch entry points: bound by libdrstencil_amd's runtime (dlopen) and used by main() below\n";
     if (p.fills_ring()) {
@@ -216,75 +233,28 @@ inline std::string plugin_api(const Schedule &s) {
         a << "    hipLaunchKernelGGL(wrap_" << p.name << ", dim3(DRS_WGRID), dim3(256), 0, stream, (real_t*)a);\n";
         a << "    return (int)hipGetLastError();\n}\n";
     }
-    const std::string wrap_in = p.fills_ring() ? "    if (int rc = drs_plugin_wrap((void*)in, stream)) return rc;\n" : "";
-    // --source kernels take three arrays: they export the _src entry points INSTEAD of the two-pointer ones
-    const std::string sfx = p.source ? "_src" : "", src_par = p.source ? ", const void* src" : "", src_arg = p.source ? ", (const real_t*)src" : "";
-    if (p.scale || p.varcoef) {
-        // --scale kernels export these two INSTEAD of every other launch entry point, with every array in their signatures: src is null unless
-        // --source, res unless --residual max, fix unless --dirichlet.  --varcoef kernels export them with ONE MORE pointer, coef, behind
-        // scale (which is null unless --scale): the runtime knows from the plan which of the two signatures a plugin has
-        const std::string res_arg = p.residual ? ", (real_t*)res" : "", fix_arg = p.dirichlet ? ", (const real_t*)fix" : "";
-        const std::string scl_arg = p.scale ? ", (const real_t*)scale" : "", coef_par = p.varcoef ? ", const void* coef" : "", coef_arg = p.varcoef ? ", (const real_t*)coef" : "";
-        a << "extern \"C\" int drs_plugin_launch_ops(const void* in, void* out, const void* src, void* res, const void* fix, const void* scale" << coef_par << ", hipStream_t stream)\n{\n" << wrap_in;
-        if (!p.source) a << "    (void)src;\n";
-        if (!p.residual) a << "    (void)res;\n";
-        if (!p.dirichlet) a << "    (void)fix;\n";
-        if (!p.scale) a << "    (void)scale;\n";
-        a << "    hipLaunchKernelGGL(dr_" << p.name << ", dim3(DRS_GRID), dim3(DRS_NTL), 0, stream, (const real_t*)in, (real_t*)out" << src_arg << res_arg << fix_arg << scl_arg << coef_arg << ");\n";
-        if (p.residual) a << "    hipLaunchKernelGGL(res_" << p.name << ", dim3(1), dim3(256), 0, stream, (real_t*)res);\n";
-        a << "    return (int)hipGetLastError();\n}\n";
-        a << "extern \"C\" int drs_plugin_launch_gold_ops(const void* in, void* out, const void* src, const void* fix, const void* scale" << coef_par << ", hipStream_t stream)\n{\n" << wrap_in;
-        if (!p.source) a << "    (void)src;\n";
-        if (!p.dirichlet) a << "    (void)fix;\n";
-        if (!p.scale) a << "    (void)scale;\n";
-        if (p.ndim == 3) a << "    dim3 b(64, 2, 2), g((N + 63) / 64, (M + 1) / 2, (L + 1) / 2);\n";
-        else a << "    dim3 b(64, 4, 1), g((N + 63) / 64, (M + 3) / 4, 1);\n";
-        a << "    hipLaunchKernelGGL(gold_" << p.name << ", g, b, 0, stream, (const real_t*)in, (real_t*)out" << src_arg << fix_arg << scl_arg << coef_arg << ");\n";
-        a << "    return (int)hipGetLastError();\n}\n";
-        a << "extern \"C\" const char* drs_plugin_info(void)\n{\n    return \"" << info_json(s) << "\";\n}\n\n";
-        return a.str();
-    }
-    if (p.dirichlet) {
-        // --dirichlet kernels export these two INSTEAD of every other launch entry point, with every array in their signatures: src is null
-        // unless --source, res unless --residual max (then res_<name> folds the partials behind the sweep, on the same stream)
-        const std::string res_arg = p.residual ? ", (real_t*)res" : "";
-        a << "extern \"C\" int drs_plugin_launch_fix(const void* in, void* out, const void* src, void* res, const void* fix, hipStream_t stream)\n{\n" << wrap_in;
-        if (!p.source) a << "    (void)src;\n";
-        if (!p.residual) a << "    (void)res;\n";
-        a << "    hipLaunchKernelGGL(dr_" << p.name << ", dim3(DRS_GRID), dim3(DRS_NTL), 0, stream, (const real_t*)in, (real_t*)out" << src_arg << res_arg << ", (const real_t*)fix);\n";
-        if (p.residual) a << "    hipLaunchKernelGGL(res_" << p.name << ", dim3(1), dim3(256), 0, stream, (real_t*)res);\n";
-        a << "    return (int)hipGetLastError();\n}\n";
-        a << "extern \"C\" int drs_plugin_launch_gold_fix(const void* in, void* out, const void* src, const void* fix, hipStream_t stream)\n{\n" << wrap_in;
-        if (!p.source) a << "    (void)src;\n";
-        if (p.ndim == 3) a << "    dim3 b(64, 2, 2), g((N + 63) / 64, (M + 1) / 2, (L + 1) / 2);\n";
-        else a << "    dim3 b(64, 4, 1), g((N + 63) / 64, (M + 3) / 4, 1);\n";
-        a << "    hipLaunchKernelGGL(gold_" << p.name << ", g, b, 0, stream, (const real_t*)in, (real_t*)out" << src_arg << ", (const real_t*)fix);\n";
-        a << "    return (int)hipGetLastError();\n}\n";
-        a << "extern \"C\" const char* drs_plugin_info(void)\n{\n    return \"" << info_json(s) << "\";\n}\n\n";
-        return a.str();
-    }
-    if (p.residual) {
-        // --residual kernels export ONE sweep entry point, with every array in its signature (src is null unless --source), INSTEAD of the others:
-        // the sweep, which writes the DRS_GRID partials d_res[1 ..], then res_<name>, which folds them into d_res[0], on the same stream
-        a << "extern \"C\" int drs_plugin_launch_res(const void* in, void* out, const void* src, void* res, hipStream_t stream)\n{\n" << wrap_in;
-        if (!p.source) a << "    (void)src;\n";
-        a << "    hipLaunchKernelGGL(dr_" << p.name << ", dim3(DRS_GRID), dim3(DRS_NTL), 0, stream, (const real_t*)in, (real_t*)out" << src_arg << ", (real_t*)res);\n";
-        a << "    hipLaunchKernelGGL(res_" << p.name << ", dim3(1), dim3(256), 0, stream, (real_t*)res);\n";
-        a << "    return (int)hipGetLastError();\n}\n";
-    } else {
-    a << "extern \"C\" int drs_plugin_launch" << sfx << "(const void* in, void* out" << src_par << ", hipStream_t stream)\n{\n" << wrap_in;
-    a << "    hipLaunchKernelGGL(dr_" << p.name << ", dim3(DRS_GRID), dim3(DRS_NTL), 0, stream, (const real_t*)in, (real_t*)out" << src_arg << ");\n";
+    // an entry point's head: every slot of its signature is a parameter, and one the kernel does not take (the caller passes NULL) is unused
+    auto head = [&](const std::string &symbol, bool gold) {
+        a << "extern \"C\" int " << symbol << "(const void* in, void* out";
+        for (int i = 0; i < NSLOTS; i++) if (abi.in_signature(i, gold)) a << ", " << slot_type(i, "void") << " " << kSlotName[i];
+        a << ", hipStream_t stream)\n{\n";
+        if (p.fills_ring()) a << "    if (int rc = drs_plugin_wrap((void*)in, stream)) return rc;\n";
+        for (int i = 0; i < NSLOTS; i++) if (abi.in_signature(i, gold) && !abi.takes[i]) a << "    (void)" << kSlotName[i] << ";\n";
+    };
+    // the sweep; with --residual max it writes the DRS_GRID partials d_res[1 ..] and res_<name> folds them into d_res[0], on the same stream
+    head(abi.sweep_symbol(), false);
+    a << "    hipLaunchKernelGGL(dr_" << p.name << ", dim3(DRS_GRID), dim3(DRS_NTL), 0, stream, (const real_t*)in, (real_t*)out" << kernel_args(abi, false) << ");\n";
+    if (p.residual) a << "    hipLaunchKernelGGL(res_" << p.name << ", dim3(1), dim3(256), 0, stream, (real_t*)res);\n";
     a << "    return (int)hipGetLastError();\n}\n";
-    }
-    if (o.pair_launch) {
+    if (abi.pair) {
         a << "extern \"C\" int drs_plugin_launch_pair(const void* in0, void* out0, const void* in1, void* out1, hipStream_t stream)\n{\n";
         a << "    hipLaunchKernelGGL(dr2_" << p.name << ", dim3(DRS_GRID, 2), dim3(DRS_NTL), 0, stream, (const real_t*)in0, (real_t*)out0, (const real_t*)in1, (real_t*)out1);\n";
         a << "    return (int)hipGetLastError();\n}\n";
     }
-    a << "extern \"C\" int drs_plugin_launch_gold" << sfx << "(const void* in, void* out" << src_par << ", hipStream_t stream)\n{\n" << wrap_in;
+    head(abi.gold_symbol(), true);
     if (p.ndim == 3) a << "    dim3 b(64, 2, 2), g((N + 63) / 64, (M + 1) / 2, (L + 1) / 2);\n";
     else a << "    dim3 b(64, 4, 1), g((N + 63) / 64, (M + 3) / 4, 1);\n";
-    a << "    hipLaunchKernelGGL(gold_" << p.name << ", g, b, 0, stream, (const real_t*)in, (real_t*)out" << src_arg << ");\n";
+    a << "    hipLaunchKernelGGL(gold_" << p.name << ", g, b, 0, stream, (const real_t*)in, (real_t*)out" << kernel_args(abi, true) << ");\n";
     a << "    return (int)hipGetLastError();\n}\n";
     a << "extern \"C\" const char* drs_plugin_info(void)\n{\n    return \"" << info_json(s) << "\";\n}\n\n";
     return a.str();
@@ -677,15 +647,16 @@ inline std::string host_main(const Schedule &s) {
     if (p.second_order) h << "    real_t* h_in = getRandomArray<real_t> (npoints);\n    real_t* h_out = getRandomArray<real_t> (npoints);   // time order 2: out holds u(t-1), input too (the rand() sequence continued)\n";
     else h << "    real_t* h_in = getRandomArray<real_t> (npoints);\n    real_t* h_out = getZeroArray<real_t> (npoints);\n";
     // --source: the third array continues the reference's rand() fill behind the arrays filled today; it lies behind the pair in the same arena
-    const bool ops = p.scale || p.varcoef;
-    const std::string launch = ops ? "drs_plugin_launch_ops" : p.dirichlet ? "drs_plugin_launch_fix" : p.residual ? "drs_plugin_launch_res" : p.source ? "drs_plugin_launch_src" : "drs_plugin_launch",
-                      gold = ops ? "drs_plugin_launch_gold_ops" : p.dirichlet ? "drs_plugin_launch_gold_fix" : p.source ? "drs_plugin_launch_gold_src" : "drs_plugin_launch_gold";
-    // --dirichlet and --scale: every array in both signatures, NULL where its option is off
-    const std::string tail = std::string(p.scale ? ", d_scale" : ", NULL") + (p.varcoef ? ", d_coef" : "");
-    const std::string gsarg = ops ? std::string(p.source ? ", src" : ", NULL") + (p.dirichlet ? ", d_fix" : ", NULL") + tail : p.dirichlet ? std::string(p.source ? ", src" : ", NULL") + ", d_fix" : p.source ? ", src" : "";       // the gold kernel computes no residual
-    const std::string sarg = ops ? std::string(p.source ? ", src" : ", NULL") + (p.residual ? ", d_res" : ", NULL") + (p.dirichlet ? ", d_fix" : ", NULL") + tail
-                           : p.dirichlet ? std::string(p.source ? ", src" : ", NULL") + (p.residual ? ", d_res" : ", NULL") + ", d_fix"
-                                         : p.residual ? (p.source ? ", src, d_res" : ", NULL, d_res") : gsarg;
+    // the entry points and what they are passed beside (in, out): every slot of the signature, NULL where the kernel takes no such array
+    const LaunchAbi abi(p);
+    const std::string launch = abi.sweep_symbol(), gold = abi.gold_symbol();
+    auto slot_args = [&](bool gold_form) {
+        std::string t;
+        for (int i = 0; i < NSLOTS; i++)
+            if (abi.in_signature(i, gold_form)) t += !abi.takes[i] ? ", NULL" : i == SLOT_SRC ? ", src" : std::string(", d_") + kSlotName[i];
+        return t;
+    };
+    const std::string sarg = slot_args(false), gsarg = slot_args(true);       // the gold kernel computes no residual
     if (p.source) h << "    real_t* h_src = getRandomArray<real_t> (npoints);   // the source term (the rand() sequence continued)\n";
     h << "    // both arrays in ONE allocation, the output " << (s.out_skew_bytes() >> 20) << " MiB (mod " << (Schedule::kPlacementPeriod >> 20) << " MiB) behind the input: launch time depends on (out - in) mod 64 MiB (--out-skew)\n";
     h << "    const size_t out_at = (nbytes + " << Schedule::kPlacementPeriod - 1 << "UL) / " << Schedule::kPlacementPeriod << "UL * " << Schedule::kPlacementPeriod << "UL + " << s.out_skew_bytes() << "UL;\n";

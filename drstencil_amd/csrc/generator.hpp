@@ -530,59 +530,32 @@ inline GenResult generate(const std::vector<std::string> &args /* argv[1..] */) 
     if (!res.plan.error.empty()) { res.messages += "Invalid configuration!\n"; res.exit_code = 255; res.error = res.plan.error; return res; }
     if (!res.plan.note.empty()) res.messages += "drstencil: note: " + res.plan.note + "\n";
     if (o.gpus < 1 || o.gpus > 64) { res.messages += "Illegal input.\n"; res.exit_code = 255; return res; }
-    if (res.plan.fills_ring() && (o.gpus > 1 || o.pair_launch)) {
-        // periodic z (y in 2D) across ranks would need a rank 0 <-> rank N-1 exchange; the pair kernel exists only for slab views
-        res.messages += "Invalid configuration!\n"; res.exit_code = 255;
-        if (res.plan.periodic)
-            res.error = o.gpus > 1 ? "--boundary periodic cannot be combined with --gpus N > 1 (the slab runtime has no periodic exchange)"
-                                   : "--boundary periodic cannot be combined with --pair-launch 1 (the pair kernel serves the slab runtime, which has no periodic exchange)";
-        else      // the slab views' rings are ghost planes of their neighbours: no view may refill its own
-            res.error = joined(boundary_words(st.ndim, res.plan.bmode, false)) +
-                        (o.gpus > 1 ? " cannot be combined with --gpus N > 1 (the slab runtime keeps every axis fixed: a slab view has no ring fill)"
-                                    : " cannot be combined with --pair-launch 1 (the pair kernel serves the slab runtime, which keeps every axis fixed)");
-        return res;
-    }
-    if (res.plan.second_order && (o.gpus > 1 || o.pair_launch)) {
-        // a slab's ghost planes are recomputed redundantly under every = 2: they would need valid old values too; the pair kernel serves the slabs
-        res.messages += "Invalid configuration!\n"; res.exit_code = 255;
-        res.error = o.gpus > 1 ? "--time-order 2 cannot be combined with --gpus N > 1 (the slab runtime keeps no old values in its ghost planes)"
-                                    : "--time-order 2 cannot be combined with --pair-launch 1 (the pair kernel serves the slab runtime, which has no second-order form)";
-        return res;
-    }
-    if (res.plan.source && (o.gpus > 1 || o.pair_launch)) {
-        // the slab views are windows of two arrays; a view of the source array is no part of the slab runtime, and the pair kernel serves it
-        res.messages += "Invalid configuration!\n"; res.exit_code = 255;
-        res.error = o.gpus > 1 ? "--source cannot be combined with --gpus N > 1 (the slab runtime passes no view of a source array)"
-                               : "--source cannot be combined with --pair-launch 1 (the pair kernel serves the slab runtime, which has no source term)";
-        return res;
-    }
-    if (res.plan.residual && (o.gpus > 1 || o.pair_launch)) {
-        // a slab rank's maximum would still have to be reduced over the ranks, and the slab runtime passes no residual array; the pair kernel serves it
-        res.messages += "Invalid configuration!\n"; res.exit_code = 255;
-        res.error = o.gpus > 1 ? "--residual cannot be combined with --gpus N > 1 (the slab runtime passes no residual array and reduces nothing over the ranks)"
-                               : "--residual cannot be combined with --pair-launch 1 (the pair kernel serves the slab runtime, which has no residual)";
-        return res;
-    }
-    if (res.plan.dirichlet && (o.gpus > 1 || o.pair_launch)) {
-        // the slab views are windows of two arrays; a view of the array of held cells is no part of the slab runtime, and the pair kernel serves it
-        res.messages += "Invalid configuration!\n"; res.exit_code = 255;
-        res.error = o.gpus > 1 ? "--dirichlet cannot be combined with --gpus N > 1 (the slab runtime passes no view of an array of held cells)"
-                               : "--dirichlet cannot be combined with --pair-launch 1 (the pair kernel serves the slab runtime, which has no held cells)";
-        return res;
-    }
-    if (res.plan.varcoef && (o.gpus > 1 || o.pair_launch)) {
-        // the slab views are windows of two arrays; views of the coefficient grids are no part of the slab runtime, and the pair kernel serves it
-        res.messages += "Invalid configuration!\n"; res.exit_code = 255;
-        res.error = o.gpus > 1 ? "--varcoef cannot be combined with --gpus N > 1 (the slab runtime passes no views of the coefficient grids)"
-                               : "--varcoef cannot be combined with --pair-launch 1 (the pair kernel serves the slab runtime, which has no coefficient arrays)";
-        return res;
-    }
-    if (res.plan.scale && (o.gpus > 1 || o.pair_launch)) {
-        // the slab views are windows of two arrays; a view of the array of factors is no part of the slab runtime, and the pair kernel serves it
-        res.messages += "Invalid configuration!\n"; res.exit_code = 255;
-        res.error = o.gpus > 1 ? "--scale cannot be combined with --gpus N > 1 (the slab runtime passes no view of an array of factors)"
-                               : "--scale cannot be combined with --pair-launch 1 (the pair kernel serves the slab runtime, which has no per-cell factor)";
-        return res;
+    if (o.gpus > 1 || o.pair_launch) {
+        // The slab runtime's views are windows of TWO arrays with every axis fixed, and the pair kernel exists only to serve it: an option
+        // with no slab form refuses both.  One row per option -- {it is on, its name, why not with --gpus N > 1, what the slab runtime
+        // lacks for --pair-launch 1} --, the first match wins.  Ring fill: periodic z (y in 2D) across ranks would need a rank 0 <->
+        // rank N-1 exchange, and a view's ring holds ghost planes of its neighbours, which no view may refill.  Time order 2: ghost planes
+        // are recomputed redundantly under every = 2 and would need valid old values too.  Residual: a rank's maximum would still have to
+        // be reduced over the ranks
+        const KernelPlan &p = res.plan;
+        struct Refusal { bool on; std::string option; const char *gpus, *pair; };
+        const Refusal rows[] = {
+            {p.fills_ring(), p.periodic ? "--boundary periodic" : joined(boundary_words(st.ndim, p.bmode, false)),
+             p.periodic ? "the slab runtime has no periodic exchange" : "the slab runtime keeps every axis fixed: a slab view has no ring fill",
+             p.periodic ? "has no periodic exchange" : "keeps every axis fixed"},
+            {p.second_order, "--time-order 2", "the slab runtime keeps no old values in its ghost planes", "has no second-order form"},
+            {p.source, "--source", "the slab runtime passes no view of a source array", "has no source term"},
+            {p.residual, "--residual", "the slab runtime passes no residual array and reduces nothing over the ranks", "has no residual"},
+            {p.dirichlet, "--dirichlet", "the slab runtime passes no view of an array of held cells", "has no held cells"},
+            {p.varcoef, "--varcoef", "the slab runtime passes no views of the coefficient grids", "has no coefficient arrays"},
+            {p.scale, "--scale", "the slab runtime passes no view of an array of factors", "has no per-cell factor"},
+        };
+        for (const Refusal &r : rows) {
+            if (!r.on) continue;
+            res.messages += "Invalid configuration!\n"; res.exit_code = 255;
+            res.error = r.option + " cannot be combined with " + (o.gpus > 1 ? std::string("--gpus N > 1 (") + r.gpus : std::string("--pair-launch 1 (the pair kernel serves the slab runtime, which ") + r.pair) + ")";
+            return res;
+        }
     }
     const Schedule sched(res.plan, o);
     if (!sched.config_error().empty()) { res.messages += "Invalid configuration!\n"; res.exit_code = 255; res.error = sched.config_error(); return res; }

@@ -288,6 +288,42 @@ struct KernelPlan {
     std::string note;        // non-empty: something the user asked for was not done (printed by the generator, kept in the banner)
 };
 
+// ---- the launch interface of a plugin: which arrays a launch takes beside in and out, in which order, through which exported symbols.
+// ONE description for the kernel signatures (emit_hip.hpp, gold_kernel), the entry points and the host program (emit_host.hpp) and the
+// runtime that binds and calls them (capi.cpp).  The slots stand in the order of every signature; a plugin exports one sweep and one gold
+// entry point, drs_plugin_launch<suffix> and drs_plugin_launch_gold<suffix>, of the family its options select:
+//   family   options                      sweep (in, out, ...)                    gold (in, out, ...)
+//   PLAIN    none of the below            -                                       -
+//   SRC      --source                     src                                     src
+//   RES      --residual max               src, res                                that of PLAIN, or of SRC with --source
+//   FIX      --dirichlet                  src, res, fix                           src, fix
+//   OPS      --scale and / or --varcoef   src, res, fix, scale[, coef]            src, fix, scale[, coef]
+// A family's signature holds every slot up to its own, whether the kernel takes it or not (a slot it does not take is passed as NULL); coef
+// is in a signature only with --varcoef; the gold kernel computes no residual, so no gold form takes res.
+enum Slot { SLOT_SRC, SLOT_RES, SLOT_FIX, SLOT_SCALE, SLOT_COEF, NSLOTS };
+inline constexpr const char *kSlotName[NSLOTS] = {"src", "res", "fix", "scale", "coef"};      // device arrays d_<name>, entry-point parameters <name>
+struct LaunchAbi {
+    enum Family { PLAIN, SRC, RES, FIX, OPS };      // the value is the number of slots in the family's sweep signature (coef apart)
+    Family sweep = PLAIN, gold = PLAIN;
+    bool takes[NSLOTS] = {};                         // the kernel takes the array
+    bool pair = false;                               // --pair-launch 1: drs_plugin_launch_pair as well (PLAIN only: every other family refuses it)
+    static const char *suffix(Family f) { static const char *const s[] = {"", "_src", "_res", "_fix", "_ops"}; return s[f]; }
+    std::string sweep_symbol() const { return std::string("drs_plugin_launch") + suffix(sweep); }
+    std::string gold_symbol() const { return std::string("drs_plugin_launch_gold") + suffix(gold); }
+    // slot i is a parameter of the sweep / gold entry point
+    bool in_signature(int i, bool gold_form) const {
+        if (gold_form && i == SLOT_RES) return false;
+        return i == SLOT_COEF ? takes[i] : i < (int)(gold_form ? gold : sweep);
+    }
+    explicit LaunchAbi(const KernelPlan &p, bool pair_launch = false) : pair(pair_launch) {
+        const bool t[NSLOTS] = {p.source, p.residual, p.dirichlet, p.scale, p.varcoef};
+        for (int i = 0; i < NSLOTS; i++) takes[i] = t[i];
+        sweep = (p.scale || p.varcoef) ? OPS : p.dirichlet ? FIX : p.residual ? RES : p.source ? SRC : PLAIN;
+        gold = sweep == RES ? (p.source ? SRC : PLAIN) : sweep;
+    }
+    LaunchAbi() = default;
+};
+
 inline int ceil_div(int a, int b) { return (a + b - 1) / b; }
 inline int round_up(int a, int b) { return ceil_div(a, b) * b; }
 

@@ -57,42 +57,25 @@ def refuse_periodic(opts, who):
                          "neighbours' planes); run it on one GPU" % (who, named))
 
 
-def refuse_second_order(opts, who):
-    """--time-order 2 has no slab form: under every = 2 the ghost planes are recomputed redundantly and would need valid old values."""
+# options with no slab form, beside the non-fixed boundaries: (the words on the command line, why not).  The slab classes pass views of
+# two arrays and nothing else, exchange planes and reduce nothing over the ranks
+NO_SLAB_FORM = (
+    (("--time-order", "2"), "redundantly computed ghost planes would need valid old values"),      # under every = 2
+    (("--source",), "it passes no view of a source array"),
+    (("--dirichlet",), "it passes no view of an array of held cells"),
+    (("--scale",), "it passes no view of an array of per-cell factors"),
+    (("--varcoef",), "it passes no views of the coefficient grids"),
+    (("--residual",), "it passes no residual array and reduces nothing over the ranks"),           # a rank's maximum would have to be reduced
+)
+
+
+def refuse_unsupported(opts, who):
+    """ValueError for generator options that have no slab form: a non-fixed boundary (refuse_periodic), then the rows of NO_SLAB_FORM."""
+    refuse_periodic(opts, who)
     opts = list(opts or ())
-    if any(a == "--time-order" and i + 1 < len(opts) and opts[i + 1] == "2" for i, a in enumerate(opts)):
-        raise ValueError("%s: --time-order 2 is not supported by the slab decomposition (redundantly computed ghost planes would need "
-                         "valid old values); run it on one GPU" % who)
-
-
-def refuse_source(opts, who):
-    """--source has no slab form: the slab classes pass views of two arrays, none of a source array."""
-    if "--source" in list(opts or ()):
-        raise ValueError("%s: --source is not supported by the slab decomposition (it passes no view of a source array); run it on one GPU" % who)
-
-
-def refuse_residual(opts, who):
-    """--residual has no slab form: a rank's maximum would have to be reduced over the ranks, and the slab classes pass no residual array."""
-    if "--residual" in list(opts or ()):
-        raise ValueError("%s: --residual is not supported by the slab decomposition (it passes no residual array and reduces nothing over the ranks); run it on one GPU" % who)
-
-
-def refuse_dirichlet(opts, who):
-    """--dirichlet has no slab form: the slab classes pass views of two arrays, none of an array of held cells."""
-    if "--dirichlet" in list(opts or ()):
-        raise ValueError("%s: --dirichlet is not supported by the slab decomposition (it passes no view of an array of held cells); run it on one GPU" % who)
-
-
-def refuse_scale(opts, who):
-    """--scale has no slab form: the slab classes pass views of two arrays, none of an array of per-cell factors."""
-    if "--scale" in list(opts or ()):
-        raise ValueError("%s: --scale is not supported by the slab decomposition (it passes no view of an array of per-cell factors); run it on one GPU" % who)
-
-
-def refuse_varcoef(opts, who):
-    """--varcoef has no slab form: the slab classes pass views of two arrays, none of the coefficient grids."""
-    if "--varcoef" in list(opts or ()):
-        raise ValueError("%s: --varcoef is not supported by the slab decomposition (it passes no views of the coefficient grids); run it on one GPU" % who)
+    for words, why in NO_SLAB_FORM:
+        if any(tuple(opts[i:i + len(words)]) == words for i in range(len(opts))):
+            raise ValueError("%s: %s is not supported by the slab decomposition (%s); run it on one GPU" % (who, " ".join(words), why))
 
 
 def slab_bounds(L, world, rank):
@@ -336,20 +319,8 @@ class HipSweep:
         """alone_opts: generator options for launches that run with NO exchange beside them (the whole-slab launch of an
         every = 2 pair): e.g. one stream block per tile, which sweeps a slab 7 % faster but whose long-lived workgroups would
         keep the RCCL send/recv kernel off the CUs."""
-        refuse_periodic(opts, "HipSweep")
-        refuse_periodic(alone_opts, "HipSweep")
-        refuse_second_order(opts, "HipSweep")
-        refuse_source(opts, "HipSweep")
-        refuse_dirichlet(opts, "HipSweep")
-        refuse_scale(opts, "HipSweep")
-        refuse_varcoef(opts, "HipSweep")
-        refuse_residual(opts, "HipSweep")
-        refuse_second_order(alone_opts, "HipSweep")
-        refuse_source(alone_opts, "HipSweep")
-        refuse_dirichlet(alone_opts, "HipSweep")
-        refuse_scale(alone_opts, "HipSweep")
-        refuse_varcoef(alone_opts, "HipSweep")
-        refuse_residual(alone_opts, "HipSweep")
+        refuse_unsupported(opts, "HipSweep")
+        refuse_unsupported(alone_opts, "HipSweep")
         self.base_stc, self.opts, self.cache_dir = base_stc, list(opts), cache_dir
         self.alone_opts = list(alone_opts) if alone_opts else None
         self.ndim = 3 if "--3d" in self.opts else 2
@@ -462,13 +433,7 @@ class SlabRun:
     def __init__(self, torch, dist, dims, H, step, iterations, rank, world, sweep, device, dtype, every=1):
         """dims = (L, M, N) for a 3D run cut along z, or (M, N) for a 2D run cut along y; every = launches per
         exchange (1 or 2, see SlabPlan)."""
-        refuse_periodic(getattr(sweep, "opts", None), "SlabRun")
-        refuse_second_order(getattr(sweep, "opts", None), "SlabRun")
-        refuse_source(getattr(sweep, "opts", None), "SlabRun")
-        refuse_dirichlet(getattr(sweep, "opts", None), "SlabRun")
-        refuse_scale(getattr(sweep, "opts", None), "SlabRun")
-        refuse_varcoef(getattr(sweep, "opts", None), "SlabRun")
-        refuse_residual(getattr(sweep, "opts", None), "SlabRun")
+        refuse_unsupported(getattr(sweep, "opts", None), "SlabRun")
         self.torch, self.dist = torch, dist
         dims = tuple(dims)
         self.plan = SlabPlan(dims[0], H, world, rank, every if world > 1 else 1)
@@ -657,20 +622,8 @@ class NativeSlabRun:
 
     def __init__(self, torch, dist, base_stc, opts, dims, H, step, iterations, rank, world, device, dtype, every=1, alone_opts=None,
                  rehearse_world=0, cache_dir=None):
-        refuse_periodic(opts, "NativeSlabRun")
-        refuse_periodic(alone_opts, "NativeSlabRun")
-        refuse_second_order(opts, "NativeSlabRun")
-        refuse_source(opts, "NativeSlabRun")
-        refuse_dirichlet(opts, "NativeSlabRun")
-        refuse_scale(opts, "NativeSlabRun")
-        refuse_varcoef(opts, "NativeSlabRun")
-        refuse_residual(opts, "NativeSlabRun")
-        refuse_second_order(alone_opts, "NativeSlabRun")
-        refuse_source(alone_opts, "NativeSlabRun")
-        refuse_dirichlet(alone_opts, "NativeSlabRun")
-        refuse_scale(alone_opts, "NativeSlabRun")
-        refuse_varcoef(alone_opts, "NativeSlabRun")
-        refuse_residual(alone_opts, "NativeSlabRun")
+        refuse_unsupported(opts, "NativeSlabRun")
+        refuse_unsupported(alone_opts, "NativeSlabRun")
         self.torch, self.dist = torch, dist
         dims = tuple(dims)
         pworld = rehearse_world or world

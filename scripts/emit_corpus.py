@@ -15,7 +15,8 @@ come from THIS tree, so whole files compare equal.  To compare with another comm
 
 The corpus: everything __graft_entry__.build() emits without a slab-view spec written into the cache; a seeded sample of the tuner's
 r3 and r4 spaces; the host-program variants; one list per value of every option that selects an emitter
-branch.  --coverage prints, per such option value, how many lists of the corpus carry it.
+branch; the nine launch interfaces with and without --check in 2D and 3D, and the rows of the refusal table for --gpus N > 1 and
+--pair-launch 1.  --coverage prints, per such option value, how many lists of the corpus carry it, and the lists per interface and row.
 """
 import argparse
 import ctypes
@@ -317,8 +318,26 @@ def varcoef_lists():
     return [(None, l) for l in lists] + [(None, j) for j in varcoef_cases.all_build_args()]       # what build() emits for the varcoef tests
 
 
+def interface_lists():
+    """The launch interfaces (csrc/plan.hpp: LaunchAbi).  What the lists in front leave open of: every one of the nine interfaces with and
+    without --check, in 2D and in 3D; a ring fill in front of the widest signature; every row of the generator's refusal table with
+    --gpus 2 and with --pair-launch 1.  --coverage counts them.  Behind everything else, so that the lists in front keep their numbers."""
+    every = ["--scale", "--varcoef", "--source", "--residual", "max", "--dirichlet"]
+    fsr = ["--dirichlet", "--source", "--residual", "max"]
+    d2, d3 = ["--dtype", "fp64"], ["--3d", "--dtype", "fp32"]
+    return [(None, l) for l in [
+        d2 + ["--residual", "max", "--source", "--check", stc("poisson2")],
+        d2 + fsr + ["--check", stc("t2_wave")], d2 + fsr + [stc("t2_star")], d2 + fsr + ["--streaming", stc("t2_star")],
+        d2 + every + ["--check", stc("lap2")], d2 + every + [stc("lap2")], d3 + every + [stc("t3_wave")],
+        d3 + every + ["--boundary", "periodic", "--check", stc("t3_wave")], d2 + every + ["--boundary-x", "reflect", stc("lap2")],
+        # rejected before the emitter is asked: the rows of the refusal table the lists in front do not reach, and both options at once
+        ["--3d", "--time-order", "2", "--gpus", "2", stc("t3_wave")], ["--3d", "--boundary", "periodic", "--pair-launch", "1", stc("t3_star")],
+        ["--3d", "--source", "--gpus", "2", "--pair-launch", "1", stc("t3_star")], ["--3d", "--dirichlet", "--scale", "--varcoef", "--pair-launch", "1", stc("t3_star")],
+    ]]
+
+
 def corpus():
-    return build_lists() + space_sample() + host_lists() + knob_lists() + boundary_lists() + source_lists() + residual_lists() + dirichlet_lists() + scale_lists() + varcoef_lists()
+    return build_lists() + space_sample() + host_lists() + knob_lists() + boundary_lists() + source_lists() + residual_lists() + dirichlet_lists() + scale_lists() + varcoef_lists() + interface_lists()
 
 
 def coverage(lists):
@@ -332,6 +351,30 @@ def coverage(lists):
             if (l[i], l[i + 1]) in seen:
                 seen[(l[i], l[i + 1])] += 1
     return seen
+
+
+INTERFACES = {"plain": (), "source": ("--source",), "residual": ("--residual",), "residual+source": ("--residual", "--source"), "dirichlet": ("--dirichlet",),
+              "dirichlet+source+residual": ("--dirichlet", "--source", "--residual"), "scale": ("--scale",), "varcoef": ("--varcoef",),
+              "scale+varcoef+source+residual+dirichlet": ("--scale", "--varcoef", "--source", "--residual", "--dirichlet")}
+ARRAY_OPTIONS = ("--source", "--residual", "--dirichlet", "--scale", "--varcoef")
+REFUSAL_ROWS = {"ring fill, periodic": lambda l: "--boundary periodic" in " ".join(l), "ring fill, other": lambda l: "--boundary" in " ".join(l) and "--boundary periodic" not in " ".join(l),
+                "time order": lambda l: "--time-order 2" in " ".join(l), "source": lambda l: "--source" in l, "residual": lambda l: "--residual" in l,
+                "dirichlet": lambda l: "--dirichlet" in l, "varcoef": lambda l: "--varcoef" in l, "scale": lambda l: "--scale" in l}
+
+
+def interface_coverage(lists):
+    """Per launch interface: lists with / without --check in 2D / 3D; per row of the refusal table: lists with --gpus N and with --pair-launch 1;
+    lists with --pair-launch 1; lists with a ring fill in front of each family's entry points."""
+    out = []
+    for name, words in INTERFACES.items():
+        mine = [l for _, l in lists if {w for w in l if w in ARRAY_OPTIONS} == set(words) and "--gpus" not in l and "--pair-launch" not in l and "--temporal" not in l]
+        n = {(c, d): sum(1 for l in mine if ("--check" in l) == c and ("--3d" in l) == d) for c in (True, False) for d in (True, False)}
+        out.append("%-42s --check 2D %3d  3D %3d   plain 2D %3d  3D %3d   ring fill %3d" % (name, n[True, False], n[True, True], n[False, False], n[False, True],
+                                                                                             sum(1 for l in mine if any(w.startswith("--boundary") for w in l))))
+    for name, has in REFUSAL_ROWS.items():
+        out.append("refused: %-22s --gpus N %3d   --pair-launch 1 %3d" % (name, sum(1 for _, l in lists if has(l) and "--gpus" in l), sum(1 for _, l in lists if has(l) and "--pair-launch" in l)))
+    out.append("--pair-launch 1 emitted lists: %d" % sum(1 for _, l in lists if "--pair-launch" in l and not any(w in l for w in ARRAY_OPTIONS + ("--boundary", "--time-order"))))
+    return out
 
 
 def main():
@@ -381,6 +424,7 @@ def main():
     if a.coverage:
         for (k, v), c in sorted(coverage(lists).items()):
             print("%4d  %s %s" % (c, k, v))
+        print("\n".join(interface_coverage(lists)))
 
 
 if __name__ == "__main__":
